@@ -16,10 +16,22 @@ same DB and minsup, median of 3 bounded samples, in the same scope as `value`
 vertical build), 1 thread (the reference's one driver thread) and all cores
 of this process's CPU share.
 
-The config-4 TSR leg (`tsr_c4`: expansions/s, its own roofline and CPU
-baseline) runs after the SPADE steps at N = 1 (--no-tsr skips it).
+A plain run does only what the headline figure needs: it builds the DB, warms
+up, times the K steps and prints the line (the per-kernel table and the
+rooflines come from the last warmup mine, so --warmup 0 leaves them out).
+--full adds everything that takes runs of its own, at N = 1: the CPU baselines
+above, the config-4 TSR leg (`tsr_c4`: expansions/s, its own roofline and CPU
+baseline; --no-tsr skips it), the config-2 complete-CPU leg (`c2_complete`;
+--no-c2 skips it) and, with --warmup 0, one instrumented mine after the timed
+steps for the kernel table.
 
-  python bench.py [--gpus N --steps K --warmup W]   (N > 1 via torch.distributed.run)
+--dump-outputs DIR writes what the last timed step returned (the pattern CSR of
+fsm_spade_mine: support, pat_off, set_off, items) as DIR/<name>.npy, float64.
+The DB is a seeded synthetic one, so two builds run with the same arguments
+mine the same input and can be compared array for array.
+
+  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
+  (N > 1 via torch.distributed.run)
 
 Prints ONE JSON line on rank 0.
 """
@@ -233,6 +245,84 @@ def tsr_leg(fsm, gen, cpu_seconds, cpu_reps, cpu):
     return leg
 
 
+ROOFLINE_KEYS = ("roofline", "roofline_k_emit", "roofline_slab", "roofline_survey_f2")
+
+
+def rooflines(ks, st):
+    """The result line's roofline objects from one mine's kernel table `ks` and stats `st`."""
+    # roofline of the dominant kernel: its work priced in SURVEY §8(d) units (12-B (sid, mask)
+    # id-list entries read + written) / its device time (HIP events on libfsm's stream, summed
+    # over the launches of the last step); the same time over the kernel's own slab bytes
+    # (24-B entries: cid, mem, lohi, pos + mask) is `roofline_slab`
+    dom = max(ks, key=lambda k: k["ms"])
+    # (the dominant kernel is k_emit or the root F2's k_f2_tri, named k_f2_keys in the table: their
+    # times are within a few percent since round 6, so the line also carries k_emit's own object)
+    dom_basis = ("SURVEY §8(d) F2 unit: 8 B per root (item, sid) entry read per F2 pass"
+                 if dom["name"] in ROOT_F2_KERNELS else
+                 "SURVEY §8(d): one 12-B (sid u32, eid mask u64) id-list entry per parent entry "
+                 "read and per child entry written (4 + 8W B for W mask words)")
+    emit = next((k for k in ks if k["name"] == "k_emit"), None)
+    achieved = (dom["survey_bytes"] / 1e9) / (dom["ms"] / 1000.0) if dom["ms"] > 0 else 0.0
+    achieved_slab = (dom["alg_bytes"] / 1e9) / (dom["ms"] / 1000.0) if dom["ms"] > 0 else 0.0
+    traffic = pmc_traffic(dom["name"])  # per step
+    traffic_launch = traffic / dom["launches"] if traffic is not None and dom["launches"] else None
+    # SURVEY §8(d) unit for the F2: 8 B per (item, sid) first/last pair read per pass,
+    # over the device time of the root F2 kernels
+    f2_ms = sum(k["ms"] for k in ks if k["name"] in ROOT_F2_KERNELS)
+    f2_bytes = 8 * st["root_entries"]
+    return {
+        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic_launch,
+                     "kernel": dom["name"], "launches_per_step": dom["launches"],
+                     "kernel_ms_per_step": dom["ms"], "alg_bytes_per_step": dom["survey_bytes"],
+                     "alg_bytes_per_launch": dom["survey_bytes"] / max(dom["launches"], 1),
+                     "traffic_per_step": traffic,
+                     "traffic_basis": "HBM bytes per launch (average over the step's launches) = "
+                                      "(2 x FETCH_SIZE + WRITE_SIZE) / launches from the committed PMC passes",
+                     "bytes_basis": dom_basis,
+                     "traffic_source": PMC_FILE if traffic is not None else None},
+        "roofline_k_emit": None if emit is None or emit["ms"] <= 0 else {
+            "bound": "hbm", "kernel": "k_emit", "unit": "GB/s", "peak": HBM_PEAK_GBS,
+            "kernel_ms_per_step": emit["ms"], "launches_per_step": emit["launches"],
+            "alg_bytes_per_step": emit["survey_bytes"],
+            "achieved": (emit["survey_bytes"] / 1e9) / (emit["ms"] / 1000.0),
+            "frac": ((emit["survey_bytes"] / 1e9) / (emit["ms"] / 1000.0)) / HBM_PEAK_GBS,
+            "traffic_per_step": pmc_traffic("k_emit"),
+            "bytes_basis": "SURVEY §8(d): one 12-B (sid u32, eid mask u64) id-list entry per parent entry "
+                           "read and per child entry written (4 + 8W B for W mask words)"},
+        "roofline_slab": {"bound": "hbm", "achieved": achieved_slab, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                          "frac": achieved_slab / HBM_PEAK_GBS, "kernel": dom["name"],
+                          "alg_bytes_per_step": dom["alg_bytes"],
+                          "bytes_basis": "the kernel's own slab layout: 16 + 8W B per entry (cid, mem, lohi, pos, "
+                                         "mask) read and written (DESIGN.md §4)"},
+        "roofline_survey_f2": {"bound": "hbm", "unit": "GB/s", "peak": HBM_PEAK_GBS,
+                               "bytes_basis": "SURVEY §8(d): 8 B per root (item, sid) entry per F2 pass",
+                               "alg_bytes": f2_bytes, "kernels_ms": f2_ms,
+                               "achieved": (f2_bytes / 1e9) / (f2_ms / 1000.0) if f2_ms else 0.0,
+                               "frac": ((f2_bytes / 1e9) / (f2_ms / 1000.0)) / HBM_PEAK_GBS if f2_ms else 0.0},
+    }
+
+
+DUMP_MAX_BYTES = 64 << 20  # all of --dump-outputs' files together
+DUMP_SEED = 20240229
+
+
+def dump_outputs(path, arrays):
+    """Write each array of `arrays` (name -> numpy array) as path/<name>.npy in float64
+    (exact for the int32 supports and items, and for int64 offsets below 2^53).  An array
+    over its equal share of DUMP_MAX_BYTES is reduced to a fixed, seeded sample of its
+    elements in index order (the same indices for the same length)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_MAX_BYTES // (8 * max(len(arrays), 1)) - 16  # elements per file, less the .npy header
+    for name, a in arrays.items():
+        a = np.asarray(a).reshape(-1)
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, size=cap, replace=False))
+            a = a[idx]
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -244,12 +334,17 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=60.0, help="bound of one CPU sample")
     ap.add_argument("--cpu-reps", type=int, default=3, help="CPU samples per leg (median; SURVEY §8d: 3)")
     ap.add_argument("--cpu-stride", type=int, default=128, help="class stride of the 1-thread CPU sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need (N = 1): the CPU baselines, the "
+                         "config-4 TSR leg, the config-2 leg, and with --warmup 0 an instrumented mine")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's pattern CSR as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     # all-cores CPU mode (SURVEY §8d ii); 0 = every CPU of this process's share (0 skips: -1)
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--dist-backend", default="nccl", help="torch.distributed backend for N > 1 (gloo: CPU dry run)")
-    ap.add_argument("--no-tsr", action="store_true", help="skip the config-4 TSR leg (N = 1 only)")
-    ap.add_argument("--no-c2", action="store_true", help="skip the config-2 complete-CPU leg (N = 1 only)")
+    ap.add_argument("--no-tsr", action="store_true", help="with --full: skip the config-4 TSR leg")
+    ap.add_argument("--no-c2", action="store_true", help="with --full: skip the config-2 complete-CPU leg")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -325,8 +420,8 @@ def main():
         eng.spade_csr(db, args.support)
     # per-kernel device times (HIP events around every launch) of the last warmup mine: the
     # timed steps run without those events (FSM_KCLOCK=0: two event records per launch cost
-    # about 0.15 ms of a D1M mine), the same mine's kernels otherwise (--warmup 0: one
-    # instrumented mine after the timed steps)
+    # about 0.15 ms of a D1M mine), the same mine's kernels otherwise (--warmup 0: with --full
+    # one instrumented mine after the timed steps, else no kernel table)
     ks = eng.kernel_stats() if args.warmup > 0 else None
 
     os.environ["FSM_KCLOCK"] = "0"
@@ -340,7 +435,9 @@ def main():
     t1 = time.perf_counter()
     del os.environ["FSM_KCLOCK"]
     st = eng.stats()  # stats of the last timed step
-    if ks is None:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(zip(("support", "pat_off", "set_off", "items"), csr)))
+    if ks is None and args.full:
         eng.spade_csr(db, args.support)
         ks = eng.kernel_stats()
 
@@ -358,7 +455,7 @@ def main():
         mine = {"rank": rank, "ms_per_step": round(ms_local, 4),
                 "ms_f1": round(st["ms_f1"], 4), "ms_f2_root": round(st["ms_f2"], 4),
                 "ms_lattice": round(st["ms_lattice"], 4), "classes": st["classes"], "entries": st["entries"],
-                "kernels": {k["name"]: round(k["ms"], 4) for k in ks}}
+                "kernels": {k["name"]: round(k["ms"], 4) for k in ks or ()}}
         per_rank = [None] * world
         dist.all_gather_object(per_rank, mine)
 
@@ -370,26 +467,6 @@ def main():
         return
 
     value = joins_all / (ms / 1000.0)  # joins of all ranks (libfsm sums them) / slowest rank
-    # roofline of the dominant kernel: its work priced in SURVEY §8(d) units (12-B (sid, mask)
-    # id-list entries read + written) / its device time (HIP events on libfsm's stream, summed
-    # over the launches of the last step); the same time over the kernel's own slab bytes
-    # (24-B entries: cid, mem, lohi, pos + mask) is `roofline_slab`
-    dom = max(ks, key=lambda k: k["ms"])
-    # (the dominant kernel is k_emit or the root F2's k_f2_tri, named k_f2_keys in the table: their
-    # times are within a few percent since round 6, so the line also carries k_emit's own object)
-    dom_basis = ("SURVEY §8(d) F2 unit: 8 B per root (item, sid) entry read per F2 pass"
-                 if dom["name"] in ROOT_F2_KERNELS else
-                 "SURVEY §8(d): one 12-B (sid u32, eid mask u64) id-list entry per parent entry "
-                 "read and per child entry written (4 + 8W B for W mask words)")
-    emit = next((k for k in ks if k["name"] == "k_emit"), None)
-    achieved = (dom["survey_bytes"] / 1e9) / (dom["ms"] / 1000.0) if dom["ms"] > 0 else 0.0
-    achieved_slab = (dom["alg_bytes"] / 1e9) / (dom["ms"] / 1000.0) if dom["ms"] > 0 else 0.0
-    traffic = pmc_traffic(dom["name"])  # per step
-    traffic_launch = traffic / dom["launches"] if traffic is not None and dom["launches"] else None
-    # SURVEY §8(d) unit for the F2: 8 B per (item, sid) first/last pair read per pass,
-    # over the device time of the root F2 kernels
-    f2_ms = sum(k["ms"] for k in ks if k["name"] in ROOT_F2_KERNELS)
-    f2_bytes = 8 * st["root_entries"]
     joins_lattice = st["joins"] - st["joins_root"]
     line = {
         "metric": "id-list joins/sec + end-to-end SPADE mine time, Quest D1M minsup 0.1%",
@@ -407,35 +484,7 @@ def main():
         "config": {"workload": "quest-C10-T2.5-S4-I1.25-D%d-N10000-seed%d, minsup %g" % (
             args.sequences, args.seed, args.support), "parallelism": "single GPU" if world == 1 else
             "prefix classes sharded over %d ranks (%s)" % (world, comm_kind)},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic_launch,
-                     "kernel": dom["name"], "launches_per_step": dom["launches"],
-                     "kernel_ms_per_step": dom["ms"], "alg_bytes_per_step": dom["survey_bytes"],
-                     "alg_bytes_per_launch": dom["survey_bytes"] / max(dom["launches"], 1),
-                     "traffic_per_step": traffic,
-                     "traffic_basis": "HBM bytes per launch (average over the step's launches) = "
-                                      "(2 x FETCH_SIZE + WRITE_SIZE) / launches from the committed PMC passes",
-                     "bytes_basis": dom_basis,
-                     "traffic_source": PMC_FILE if traffic is not None else None},
-        "roofline_k_emit": None if emit is None or emit["ms"] <= 0 else {
-            "bound": "hbm", "kernel": "k_emit", "unit": "GB/s", "peak": HBM_PEAK_GBS,
-            "kernel_ms_per_step": emit["ms"], "launches_per_step": emit["launches"],
-            "alg_bytes_per_step": emit["survey_bytes"],
-            "achieved": (emit["survey_bytes"] / 1e9) / (emit["ms"] / 1000.0),
-            "frac": ((emit["survey_bytes"] / 1e9) / (emit["ms"] / 1000.0)) / HBM_PEAK_GBS,
-            "traffic_per_step": pmc_traffic("k_emit"),
-            "bytes_basis": "SURVEY §8(d): one 12-B (sid u32, eid mask u64) id-list entry per parent entry "
-                           "read and per child entry written (4 + 8W B for W mask words)"},
-        "roofline_slab": {"bound": "hbm", "achieved": achieved_slab, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                          "frac": achieved_slab / HBM_PEAK_GBS, "kernel": dom["name"],
-                          "alg_bytes_per_step": dom["alg_bytes"],
-                          "bytes_basis": "the kernel's own slab layout: 16 + 8W B per entry (cid, mem, lohi, pos, "
-                                         "mask) read and written (DESIGN.md §4)"},
-        "roofline_survey_f2": {"bound": "hbm", "unit": "GB/s", "peak": HBM_PEAK_GBS,
-                               "bytes_basis": "SURVEY §8(d): 8 B per root (item, sid) entry per F2 pass",
-                               "alg_bytes": f2_bytes, "kernels_ms": f2_ms,
-                               "achieved": (f2_bytes / 1e9) / (f2_ms / 1000.0) if f2_ms else 0.0,
-                               "frac": ((f2_bytes / 1e9) / (f2_ms / 1000.0)) / HBM_PEAK_GBS if f2_ms else 0.0},
+        **(rooflines(ks, st) if ks else dict.fromkeys(ROOFLINE_KEYS)),  # no kernel table: plain --warmup 0
         "extra": {"mine_ms": ms, "joins": joins_all, "patterns": meta["n"], "minsup": meta["minsup"],
                   "joins_root": st["joins_root"], "joins_lattice": joins_lattice,
                   "root_pair_joins_executed": st["root_keys"], "lattice_pair_tests": st["pair_tests"],
@@ -450,11 +499,11 @@ def main():
                   "join_equiv_GBps": (st["bytes_join_equiv"] / 1e9) / (ms / 1000.0),
                   "kernels": sorted(({"name": k["name"], "launches": k["launches"], "ms": round(k["ms"], 4),
                                       "GBps": round((k["alg_bytes"] / 1e9) / (k["ms"] / 1000.0), 1) if k["ms"] else 0}
-                                     for k in ks), key=lambda k: -k["ms"])},
+                                     for k in ks or ()), key=lambda k: -k["ms"])},
     }
     if per_rank is not None:
         line["extra"]["per_rank"] = per_rank
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         host = "%s; nproc %d, this process's CPU share %d" % (cpu_model(), os.cpu_count() or 0, cpu_share())
         cb = cpu_baseline(ds, args.support, args.cpu_seconds, 1, args.cpu_reps, args.cpu_stride)
         cb["sample"] = ("same DB and minsup; the single-thread CPU restatement (oracle/fsm_oracle.c) mining every "
@@ -471,9 +520,9 @@ def main():
             line["extra"]["cpu_baseline_all_cores"] = ca
     db.free()
     eng.close()
-    if not args.no_tsr and world == 1:
+    if args.full and not args.no_tsr and world == 1:
         line["tsr_c4"] = tsr_leg(fsm, gen, args.cpu_seconds, args.cpu_reps, not args.no_cpu_baseline)
-    if not args.no_c2 and not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_c2 and not args.no_cpu_baseline and world == 1:
         line["c2_complete"] = c2_leg(fsm, gen, args.cpu_reps)
     print(json.dumps(line), flush=True)
     if world > 1:

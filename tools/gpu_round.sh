@@ -18,7 +18,8 @@ if [ "${SKIP_EV:-0}" != 1 ]; then
   tail -1 gpurun_out/ev.log
 fi
 if [ "${SKIP_BENCH:-0}" != 1 ]; then
-  timeout -k 10 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/bench.json 2> gpurun_out/bench.err || { echo BENCHFAIL; tail -20 gpurun_out/bench.err; exit 1; }
-  python3 -c "import json; d=json.load(open('gpurun_out/bench.json')); print('bench', d['ms_per_step'], d['value'], d['roofline']['kernel'], d['roofline']['frac'])"
+  BENCH_JSON=${BENCH_JSON:-$TMPDIR/bench.json}  # the complete line: CPU baselines, TSR c4 and config-2 legs
+  timeout -k 10 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > "$BENCH_JSON" 2> "$BENCH_JSON.err" || { echo BENCHFAIL; tail -20 "$BENCH_JSON.err"; exit 1; }
+  python3 -c "import json, sys; d=json.load(open(sys.argv[1])); print('bench', d['ms_per_step'], d['value'], d['roofline']['kernel'], d['roofline']['frac'])" "$BENCH_JSON"
 fi
 exit 0
