@@ -487,8 +487,10 @@ __device__ __forceinline__ uint64_t lane_range(uint32_t a, uint32_t b) {  // bit
 // cycles waiting to issue) and the per-run key walk latency bound (93 % waiting).
 __device__ __forceinline__ uint32_t rfl(uint32_t v) { return uint32_t(__builtin_amdgcn_readfirstlane(int(v))); }
 
-// rank -> group by multiply-high (exact for rank < 2^16, per < 2^15)
-__device__ __forceinline__ uint32_t group_of(uint32_t rank, uint32_t pm) { return __umulhi(rank, pm); }
+// rank -> group by multiply-high (exact for rank < 2^16, per < 2^15).  One row per group (a counter
+// row of more than half a group: over 8,192 frequent items) makes the multiplier 2^32, which the u32
+// holds as 0: the group is then the rank itself
+__device__ __forceinline__ uint32_t group_of(uint32_t rank, uint32_t pm) { return pm ? __umulhi(rank, pm) : rank; }
 
 // region (group g, row block b) in scan order: group-major [g][b], each group's keys one
 // contiguous stream for k_f2_count (block-major measured no faster)

@@ -1,0 +1,728 @@
+"""Threshold-tight databases placed on the kernels' geometry constants.
+
+TEST INFRASTRUCTURE ONLY (plain Python, no GPU).  Two ideas:
+
+* threshold-tight: every candidate the miner counts is exactly at the
+  threshold (support == minsup) or exactly one below it, so a count that is
+  off by one anywhere (a pair counted twice, one sequence's contribution
+  dropped) changes the frequent set instead of hiding behind a margin;
+* the generators say where their rows and runs fall (`geometry`), so a test
+  can assert that its DB really has the length / offset it is named after
+  (a 64-entry run at lane 0, a run that starts at range - 1, ...).
+
+Families: `tight_spade` (hub sequences), `wide_mask_db` (one sequence of E
+itemsets), `big_row_db` (one DB row of n entries), `tsr_long_rows`,
+`tsr_sid_edges`, and `k0_image`, the DB image by definition from the token
+rules (SPADE.scala:53-106, :151-210; TSR.scala:52-94, :109-143).
+"""
+import os
+import random
+import re
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ENGINE_SRC = os.path.join(ROOT, "spark-fsm_amd", "csrc", "spade_engine.hip")
+
+
+class EdgeDB:
+    """A database as token rows (-1 closes an itemset, -2 ends the row), with
+    the views the engine and the oracle take: SPMF text records and the token
+    arrays (sids 0..N-1)."""
+
+    def __init__(self, rows, name=""):
+        self.rows = rows
+        self.name = name
+        lens = [len(r) for r in rows]
+        self.seq_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        self.tokens = np.fromiter((t for r in rows for t in r), dtype=np.int64, count=int(self.seq_off[-1]))
+        self.sids = np.arange(len(rows), dtype=np.int32)
+
+    def __len__(self):
+        return len(self.rows)
+
+    def records(self):
+        return [(s, " ".join(map(str, r))) for s, r in enumerate(self.rows)]
+
+    @property
+    def support(self):
+        """The relative support that makes minsup = ceil(support * N) = 2."""
+        return 1.5 / len(self.rows)
+
+
+def _row(itemsets, end=True):
+    out = []
+    for s in itemsets:
+        out.extend(s)
+        out.append(-1)
+    if end:
+        out.append(-2)
+    return out
+
+
+def itemsets_of(row):
+    """Closed itemsets of a token row, empty ones included (TSR indexes count them)."""
+    sets, cur = [], []
+    for t in row:
+        if t == -1:
+            sets.append(cur)
+            cur = []
+        elif t != -2:
+            cur.append(t)
+    return sets
+
+
+# ---------------------------------------------------------------- SPADE hubs
+def _selected_ranks(n):
+    """Rank pairs (a < b) of a hub of n items that get a private two-item
+    sequence: first, last, middle, middle +- 1 and their neighbours (at most 8)."""
+    if n < 2:
+        return []
+    m = n // 2
+    cand = [(0, 1), (n - 2, n - 1), (0, n - 1), (m - 1, m), (m, m + 1), (0, m), (m, n - 1), (1, n - 2)]
+    out = []
+    for a, b in cand:
+        if 0 <= a < b < n and (a, b) not in out:
+            out.append((a, b))
+    return out
+
+
+class TightSpade(EdgeDB):
+    """tight_spade's result: the DB plus what it claims about itself.
+
+    selected      {pattern: 2}: the planted multi-item patterns over hub items
+                  (without the common prefix), every one at support 2
+    singles       {item: support} of every frequent non-prefix item
+    prefix_items  the common one-item itemsets A1..Ad heading every sequence
+    hub_rows      row index of each hub
+    hub_items     per hub: its frequent items in ascending value (rank) order
+    rest_sample   per hub: pairs of ranks (first, last, middle ...) that were NOT selected
+    """
+
+    def expected(self):
+        """The complete frequent set at minsup 2, in closed form: every ordered
+        sub-chain of the prefix, alone (support N) or followed by a frequent
+        single item or a selected pattern (their own supports)."""
+        N = len(self.rows)
+        base = {((i,),): s for i, s in self.singles.items()}
+        base.update(self.selected)
+        d = len(self.prefix_items)
+        out = dict(base)
+        for bits in range(1, 1 << d):
+            chain = tuple((self.prefix_items[k],) for k in range(d) if bits >> k & 1)
+            out[chain] = N
+            for p, s in base.items():
+                out[chain + p] = s
+        return sorted(out.items())
+
+    def root_entries(self):
+        """(frequent item, sequence) entries of the root class at minsup 2."""
+        freq = set(self.singles) | set(self.prefix_items)
+        return sum(len({t for t in r if t >= 0} & freq) for r in self.rows)
+
+
+def tight_spade(lengths, per_set=1, lead=0, prefix=0, pad=0, noise=0, dup=False, filler=0, hub_last=False, seed=1):
+    """The hub family.  For each n in `lengths` one hub sequence holds n fresh
+    items, `per_set` per itemset, in shuffled order (rank is not position).
+    Each item has one private single-item sequence (support 2); a few pairs
+    chosen by rank (`_selected_ranks`) have one private two-item sequence that
+    repeats the pair's relation in the hub (x -> y, or (x y) in one itemset),
+    and with `dup` the lowest item of each hub is placed twice and x -> x is
+    selected.  At minsup 2 every selected relation has support exactly 2, every
+    other pair of a hub exactly 1, and no triple of hub items reaches 2.
+
+    prefix = d  prepends the one-item itemsets A1 .. Ad (items 1..d, the lowest
+                ranks) to every sequence: the same structure reappears in the
+                classes [A1], [A1 -> A2], ...
+    lead = j    (int, or one per hub) puts j filler sequences right before that
+                hub; pad = p puts p prefix-only sequences before the first hub
+                (root run d, [A1] run d - 1): together they place a run start
+    filler = F  at least F frequent filler items, two single-item sequences each
+    noise = m   m infrequent items interleaved (by value and by itemset) in
+                every hub: the DB row grows past its frequent entries
+    hub_last    the last hub is the last sequence (its runs end at E)
+    """
+    rng = random.Random(seed)
+    lengths = list(lengths)
+    leads = [lead] + [0] * (len(lengths) - 1) if isinstance(lead, int) else list(lead)
+    assert len(leads) == len(lengths)
+    d = prefix
+    pre = [[a] for a in range(1, d + 1)]
+    nfill = max(filler, (sum(leads) + 1) // 2)
+    fill_items = list(range(d + 1, d + 1 + nfill))
+    fill_rows = [_row(pre + [[f]]) for f in fill_items for _ in (0, 1)]
+    base = d + 1 + nfill
+    rows, hub_rows, hub_items, rest = [_row(pre) for _ in range(pad)] if d else [], [], [], []
+    assert d or not pad
+    singles = {f: 2 for f in fill_items}
+    selected, tail, fi = {}, [], 0
+    for n, j in zip(lengths, leads):
+        items = [base + 2 * i for i in range(n)]
+        noise_items = [base + 2 * (i * n // max(noise, 1)) + 1 for i in range(noise)]
+        assert len(set(noise_items)) == noise
+        base += 2 * n + 2
+        order = items[:]
+        rng.shuffle(order)
+        sets = [sorted(order[k:k + per_set]) for k in range(0, n, per_set)]
+        for k, z in enumerate(noise_items):
+            sets[k % len(sets)].append(z)
+        where = {x: k for k, s in enumerate(sets) for x in s}
+        if dup:
+            sets.append([items[0]])
+        for x in items:
+            singles[x] = 2
+            tail.append(_row(pre + [[x]]))
+        sel = _selected_ranks(n)
+        for a, b in sel:
+            x, y = items[a], items[b]
+            if where[x] == where[y]:
+                p = ((x, y),)
+            elif where[x] < where[y]:
+                p = ((x,), (y,))
+            else:
+                p = ((y,), (x,))
+            selected[p] = 2
+            singles[x] += 1
+            singles[y] += 1
+            tail.append(_row(pre + [list(s) for s in p]))
+        if dup:
+            x = items[0]
+            selected[((x,), (x,))] = 2
+            singles[x] += 1
+            tail.append(_row(pre + [[x], [x]]))
+        m = n // 2
+        rest.append([(a, b) for a, b in [(0, 2), (n - 3, n - 1), (m - 2, m), (m - 1, m + 1), (0, n - 2), (1, n - 1), (1, m)]
+                     if 0 <= a < b < n and (a, b) not in sel])
+        rows.extend(fill_rows[fi:fi + j])
+        fi += j
+        hub_rows.append(len(rows))
+        hub_items.append(items)
+        rows.append(_row(pre + sets))
+    rest_rows = fill_rows[fi:] + tail
+    rng.shuffle(rest_rows)
+    if hub_last:
+        hub = rows.pop()
+        rows.extend(rest_rows)
+        hub_rows[-1] = len(rows)
+        rows.append(hub)
+    else:
+        rows.extend(rest_rows)
+    db = TightSpade(rows, "tight%s/%d" % (lengths, per_set))
+    db.kw = dict(lengths=lengths, per_set=per_set, lead=lead, prefix=prefix, pad=pad, noise=noise, dup=dup,
+                 filler=filler, hub_last=hub_last, seed=seed)
+    db.selected, db.singles, db.prefix_items = selected, singles, list(range(1, d + 1))
+    db.hub_rows, db.hub_items, db.rest_sample = hub_rows, hub_items, rest
+    return db
+
+
+def closed_form_ref(db):
+    """The oracle's answer for a large filler DB (prefix = 1) without mining it: the patterns are
+    expected(); the joins are those of the root (F members: F^2 + F (F - 1) / 2) and of [A1]
+    (F - 1 members) plus a constant of the hub structure, which filler items do not touch; the
+    constant is read off the oracle's join count on the same DB built with 20 filler items
+    (tests/test_edge_dbs.py checks the form against the oracle at sizes it can mine quickly)."""
+    from oracle import oracle
+    assert db.kw["prefix"] == 1 and not db.kw["pad"] and not db.kw["lead"]
+
+    def base(F):
+        return F * F + F * (F - 1) // 2 + (F - 1) * (F - 1) + (F - 1) * (F - 2) // 2
+    twin = tight_spade(**dict(db.kw, filler=20))
+    F0, F = len(twin.singles) + 1, len(db.singles) + 1
+    c = oracle.spade_tokens(twin.seq_off, twin.tokens, twin.support)["joins"] - base(F0)
+    return {"patterns": db.expected(), "joins": base(F) + c, "minsup": 2}
+
+
+def relation(db, hub, a, b):
+    """The pair of ranks (a, b) of a hub as the pattern the hub itself holds."""
+    sets = itemsets_of(db.rows[db.hub_rows[hub]])
+    x, y = db.hub_items[hub][a], db.hub_items[hub][b]
+    wx = next(k for k, s in enumerate(sets) if x in s)
+    wy = next(k for k, s in enumerate(sets) if y in s)
+    if wx == wy:
+        return ((min(x, y), max(x, y)),)
+    return ((x,), (y,)) if wx < wy else ((y,), (x,))
+
+
+def place(level, start, prefix):
+    """(lead, pad) for tight_spade so that the first hub's run starts at entry
+    `start` of the root class (level 0: a filler sequence is a run of
+    prefix + 1, a prefix-only one of prefix) or of [A1] (level 1: prefix and
+    prefix - 1).  geometry() then confirms the placement."""
+    big = prefix + 1 - level
+    small = big - 1
+    if small == 0:
+        assert start % big == 0
+        return start // big, 0
+    for pad in range(0, big):
+        if (start - pad * small) >= 0 and (start - pad * small) % big == 0:
+            return (start - pad * small) // big, pad
+    raise AssertionError("no placement")
+
+
+# ---------------------------------------------------------------- geometry
+def wave_ranges():
+    """Entries per wave range of k_emit2 (root, W = 1 lattice, W > 1 lattice)
+    and of k_count2, read from the engine source's own #define lines."""
+    with open(ENGINE_SRC) as f:
+        src = f.read()
+    out = {}
+    for key, name in (("root", "FSM_E2_RANGE_ROOT"), ("lattice", "FSM_E2_RANGE"), ("lattice_w", "FSM_E2_RANGE_W"),
+                      ("count2", "FSM_C2_RANGE")):
+        m = re.search(r"^#define\s+%s\s+(\d+)\b" % name, src, re.M)
+        assert m, "no #define %s in spade_engine.hip" % name
+        out[key] = int(m.group(1))
+    return out
+
+
+def geometry(rows, minsup, classes=True):
+    """Run layout by definition.  A class is stored one run per sequence that
+    contains its prefix, one entry per member present, sequences in sid order.
+
+    root     [(start, length)]: frequent items of each sequence (the root slab)
+    root_db  the same over all distinct items (the DB rows the DB-direct root reads)
+    classes  {A: [(start, length)]} for each frequent item A: the members
+             A -> x and (A x) with support >= minsup present in each sequence
+    E        entries in all (root, root_db, and per class)
+    """
+    seqs = []
+    for r in rows:
+        fl = {}
+        for k, s in enumerate(x for x in itemsets_of(r) if x):
+            for it in s:
+                f = fl.setdefault(it, [k, k, set()])
+                f[1] = k
+                f[2].add(k)
+        seqs.append(fl)
+    sup = {}
+    for fl in seqs:
+        for it in fl:
+            sup[it] = sup.get(it, 0) + 1
+    freq = {i for i, c in sup.items() if c >= minsup}
+
+    def runs(lens):
+        out, at = [], 0
+        for n in lens:
+            if n:
+                out.append((at, n))
+            at += n
+        return out, at
+
+    g = {"ranges": wave_ranges()}
+    g["root"], g["E_root"] = runs(len(freq & set(fl)) for fl in seqs)
+    g["root_db"], g["E_db"] = runs(len(fl) for fl in seqs)
+    if not classes:
+        return g
+    psup, present = {}, []
+    for fl in seqs:
+        mem = {}
+        its = sorted(i for i in fl if i in freq)
+        for a in its:
+            fa = fl[a]
+            for x in its:
+                fx = fl[x]
+                if fa[0] < fx[1]:
+                    mem.setdefault(a, []).append((x, 0))
+                if x > a and fa[2] & fx[2]:
+                    mem.setdefault(a, []).append((x, 1))
+        present.append(mem)
+        for a, ms in mem.items():
+            for m in ms:
+                psup[(a, m)] = psup.get((a, m), 0) + 1
+    g["classes"], g["E_class"] = {}, {}
+    for a in sorted(freq):
+        g["classes"][a], g["E_class"][a] = runs(
+            sum(1 for m in mem.get(a, ()) if psup[(a, m)] >= minsup) for mem in present)
+    return g
+
+
+def run_at(runs, start=None, length=None, end=None):
+    """The runs of a layout with the given start / length / end (any of them)."""
+    return [(s, n) for s, n in runs if (start is None or s == start) and (length is None or n == length)
+            and (end is None or s + n == end)]
+
+
+# ---------------------------------------------------------------- wide masks
+class Planted(EdgeDB):
+    def expected(self):
+        out = {((i,),): s for i, s in self.singles.items()}
+        out.update(self.selected)
+        return sorted(out.items())
+
+    def root_entries(self):
+        freq = set(self.singles)
+        return sum(len({t for t in r if t >= 0} & freq) for r in self.rows)
+
+
+def _plant(rows_before, big, planted_at, name):
+    """Shared tail of wide_mask_db / big_row_db: `big` is the long sequence as
+    itemsets, planted_at {item: itemset index}; every planted item gets a
+    private sequence, the neighbouring planted pairs and (first, last) get a
+    private two-item sequence repeating their relation, the other pairs stay
+    at support 1."""
+    its = sorted(planted_at, key=lambda i: (planted_at[i], i))
+    singles = {i: 2 for i in its}
+    sel = [(its[k], its[k + 1]) for k in range(0, len(its) - 1, 2)]
+    if len(its) > 2:
+        sel.append((its[0], its[-1]))
+    if len(its) > 3:
+        sel.append((its[1], its[-2]))
+    if len(its) > 1 and planted_at[its[-2]] == planted_at[its[-1]] and (its[-2], its[-1]) not in sel:
+        sel.append((its[-2], its[-1]))
+    selected, tail = {}, [_row([[i]]) for i in its]
+    for x, y in sel:
+        p = ((min(x, y), max(x, y)),) if planted_at[x] == planted_at[y] else ((x,), (y,))
+        selected[p] = 2
+        singles[x] += 1
+        singles[y] += 1
+        tail.append(_row([list(s) for s in p]))
+    rest = [(x, y) for a, x in enumerate(its) for y in its[a + 1:] if (x, y) not in sel]
+    db = Planted(rows_before + [_row(big, end=False)] + tail, name)
+    db.selected, db.singles, db.planted_at, db.rest_pairs, db.big_row = selected, singles, planted_at, rest, len(rows_before)
+    return db
+
+
+def wide_mask_db(E, shared_last=True):
+    """One sequence of exactly E non-empty itemsets, each one unique (infrequent)
+    noise item, except that planted items 1..6 take the itemsets at eids 0, 1,
+    63, 64, E - 2, E - 1 (those below E, once each); with `shared_last` item 7
+    shares the last itemset.  Without it the row is exactly 2 E tokens (at
+    E = 4,096 the 8,192 tokens of the longest row the device build takes)."""
+    big = [[1000 + k] for k in range(E)]
+    planted_at = {}
+    for it, e in zip(range(1, 7), (0, 1, 63, 64, E - 2, E - 1)):
+        if 0 <= e < E and e not in planted_at.values():
+            planted_at[it] = e
+            big[e] = [it]
+    if shared_last:
+        planted_at[7] = E - 1
+        big[E - 1].append(7)
+    db = _plant([_row([[8]]), _row([[8]])], big, planted_at, "wide-mask-%d" % E)
+    db.singles[8] = 2
+    return db
+
+
+def big_row_db(n, nsets=60):
+    """One DB row of exactly n distinct items over `nsets` itemsets (W = 1), three
+    of them frequent: the lowest, the middle and the highest value of the row."""
+    vals = list(range(10, 10 + n))
+    big = [vals[k::nsets] for k in range(nsets)]
+    big = [s for s in big if s]
+    planted = (vals[0], vals[n // 2], vals[-1])
+    planted_at = {it: next(k for k, s in enumerate(big) if it in s) for it in planted}
+    assert len(planted_at) == 3
+    return _plant([], big, planted_at, "big-row-%d" % n)
+
+
+def planted_relation(db, x, y):
+    ax, ay = db.planted_at[x], db.planted_at[y]
+    if ax == ay:
+        return ((min(x, y), max(x, y)),)
+    return ((x,), (y,)) if ax < ay else ((y,), (x,))
+
+
+# ---------------------------------------------------------------- TSR
+def tsr_long_rows(T, N=8, tight=(), short_between=0):
+    """All N sequences hold items 1, 2, 3 in itemsets 0, 1, 2 (five rules of
+    support N among them).  Tail item j (10 + j, j < T) sits in itemset 0 in half
+    of the sequences and in itemset 3 in the other half; a tail item listed in
+    `tight` (by j) sits in itemset 0 in N - 1 sequences and in itemset 3 in one.
+    Every tail item has support N; every rule with a tail item has support
+    <= N - 1 (t -> 2, t -> 3 reach exactly N - 1 for a tight t).
+    short_between = m puts m sequences <2, 1> after each long one: they are in
+    the domain of every rule over 1 and 2 (one-entry rows between the long ones)
+    and add the rule 2 -> 1 above the threshold, which stays N."""
+    tight = set(tight)
+    rows = []
+    for s in range(N):
+        head, back = [1], []
+        for j in range(T):
+            if j in tight:
+                at0 = s != j % N
+            else:
+                at0 = (s + j) % 2 == 0
+            (head if at0 else back).append(10 + j)
+        rows.append(_row([head, [2], [3], back]))
+        for _ in range(short_between):
+            rows.append(_row([[2], [1]]))
+    db = EdgeDB(rows, "tsr-long-%d" % T)
+    db.T, db.N, db.tight = T, N, sorted(tight)
+    return db
+
+
+SID_EDGES = (31, 32, 127, 128, 1023, 1024, 32767, 32768)
+
+
+def tsr_sid_edges(N):
+    """Six items, N sequences.  Rule 1 -> 2 holds exactly at sids 0, 1, the edge
+    sids below N (SID_EDGES) and N - 1: support m.  Rule 3 -> 4 holds at m - 1
+    other sids.  Every other sequence holds one item alone (2, 3, 5 or 6: no rule),
+    so with minconf 0 and k = 1 the answer is 1 -> 2 alone, and it is lost or
+    tied as soon as one deciding sid is not counted; k = 2 returns both."""
+    deciding = sorted({0, 1, N - 1} | {e for e in SID_EDGES if e < N})
+    m = len(deciding)
+    others = [s for s in range(2, N) if s not in deciding]
+    step = max(1, len(others) // (m - 1))
+    second = others[::step][:m - 1]
+    assert len(second) == m - 1
+    rows = []
+    for s in range(N):
+        if s in deciding:
+            rows.append(_row([[1], [2]]))
+        elif s in second:
+            rows.append(_row([[3], [4]]))
+        else:
+            rows.append(_row([[(2, 3, 5, 6)[s % 4]]]))
+    db = EdgeDB(rows, "tsr-sids-%d" % N)
+    db.deciding, db.second = deciding, second
+    return db
+
+
+def tsr_deep_index(last_index):
+    """Two sequences whose last itemset index is `last_index` (empty itemsets in
+    between count), plus short ones: rules 1 -> 2 (support 3) and 1 -> 3, 3 -> 2
+    (support 2) across the whole index range."""
+    deep = [1, -1] + [-1] * (last_index - 2) + [3, -1, 2, -1, -2]
+    assert len(itemsets_of(deep)) == last_index + 1
+    return EdgeDB([deep, list(deep), _row([[1], [2]]), _row([[2], [1]])], "tsr-deep-%d" % last_index)
+
+
+# ---------------------------------------------------------------- K0 image
+def k0_image(rows, mode):
+    """The DB image by definition, as fsm_db_export lays it out.  mode "spade":
+    -1 closes an itemset, -2 is ignored, items after the last -1 are dropped; an
+    entry per distinct item of a row in ascending value, its mask the set of
+    eids (rank of the itemset among the row's non-empty closed itemsets) it
+    occurs at; mask_words the smallest power of two covering the longest row's
+    eids; max_occ the most closed item tokens of one row.  mode "tsr": an
+    entry's first / last are the 0-based itemset indexes counting every -1.
+    Item ids are dense ranks over the values of all entries."""
+    ent = []  # per row: sorted [(value, eids)]
+    max_eids = max_occ = 0
+    for r in rows:
+        closed, cur = [], []
+        for t in r:
+            if t == -1:
+                closed.append(cur)
+                cur = []
+            elif t != -2:
+                cur.append(int(t))
+        occ = {}
+        if mode == "spade":
+            closed = [s for s in closed if s]
+            max_occ = max(max_occ, sum(len(s) for s in closed))
+        max_eids = max(max_eids, len(closed))
+        for e, s in enumerate(closed):
+            for it in s:
+                occ.setdefault(it, []).append(e)
+        ent.append(sorted(occ.items()))
+    vals = sorted({v for row in ent for v, _ in row})
+    dense = {v: k for k, v in enumerate(vals)}
+    E = sum(len(row) for row in ent)
+    img = {"rows": len(rows), "entries": E, "items": len(vals),
+           "row_off": np.concatenate([[0], np.cumsum([len(row) for row in ent])]).astype(np.uint32),
+           "item": np.array([dense[v] for row in ent for v, _ in row], dtype=np.uint32),
+           "item_val": np.array(vals, dtype=np.int32)}
+    if mode == "spade":
+        W = 1
+        while W * 64 < max_eids:
+            W *= 2
+        mask = np.zeros((E, W), dtype=np.uint64)
+        q = 0
+        for row in ent:
+            for _, es in row:
+                for e in es:
+                    mask[q, e >> 6] |= np.uint64(1 << (e & 63))
+                q += 1
+        img.update(mask_words=W, max_occ=max_occ, mask=mask.reshape(-1))
+    else:
+        img["first"] = np.array([es[0] for row in ent for _, es in row], dtype=np.uint32)
+        img["last"] = np.array([es[-1] for row in ent for _, es in row], dtype=np.uint32)
+    return img
+
+
+# ---------------------------------------------------------------- case tables
+# The DBs of tests/test_edges_gpu.py, built once per process; tests/test_edge_dbs.py
+# proves the claims (tightness, geometry) of the very same objects without a GPU.
+F2_LENGTHS = (1, 2, 3, 4, 15, 16, 17, 31, 32, 33, 62, 63, 64, 65, 66, 127, 128, 129)
+LATTICE_SHORT = (63, 64, 65, 66)
+LATTICE_LONG = (127, 128, 129, 192, 193, 256, 257)
+RK_SIZES = (2047, 2048, 2049, 4096, 4097)
+FREQ_RECS_ROWS = 16385
+MASK_E = (63, 64, 65, 128, 129, 4096, 4097, 65535, 65536)
+MASK_W = (1, 1, 2, 2, 4, 64, 128, 1024, 1024)
+TSR_T = (4095, 4096, 4097, 4200, 8300)
+TSR_N = (31, 32, 33, 127, 128, 129, 1023, 1024, 1025, 32767, 32768, 32769)
+
+_CACHE = {}
+
+
+def _cached(key, make):
+    if key not in _CACHE:
+        _CACHE[key] = make()
+    return _CACHE[key]
+
+
+def hub_run(db, g, hub, level):
+    """(start, length) of hub `hub`'s run in the root class (level 0, the slab
+    layout), in the DB rows (level "db") or in [A1] (level 1)."""
+    layout = g["classes"].get(1, []) if level == 1 else g["root_db" if level == "db" else "root"]
+    # runs are listed for sequences with entries: in these families every sequence has some
+    assert len(layout) == len(db.rows), "a sequence without entries: runs are not row-aligned"
+    return layout[db.hub_rows[hub]]
+
+
+def f2_cases():
+    """Family 1, root F2 row lengths: (name, db, {hub: DB row length})."""
+    def make():
+        out = []
+        db = tight_spade(F2_LENGTHS, per_set=3, seed=2)
+        out.append(("all", db, {h: n for h, n in enumerate(F2_LENGTHS)}))
+        ns = (15, 32, 33, 61, 62, 63, 64)
+        db = tight_spade(ns, per_set=3, noise=3, seed=3)  # rl > 64 with n <= 64 frequent
+        out.append(("noise", db, {h: n + 3 for h, n in enumerate(ns)}))
+        ns = (3, 4, 63, 64, 65)
+        db = tight_spade(ns, per_set=3, dup=True, seed=4)
+        out.append(("dup", db, {h: n for h, n in enumerate(ns)}))
+        return out
+    return _cached("f2", make)
+
+
+def lattice_cases(w):
+    """Family 2, lattice windows at mask width w (1 or 2), prefix = 2:
+    (name, db, level, claim) where claim is a dict of geometry facts to assert:
+    {"length": L} for hub 0's run at `level`, {"start": s}, {"end_is_E": True}."""
+    def make():
+        out = []
+        d = 2
+        # run lengths: a hub of n items is a run of n + 2 in the root, n + 1 in [A1], n in [A1 -> A2]
+        ns = sorted({L - k for L in LATTICE_SHORT + LATTICE_LONG for k in (0, 1)})
+        if w == 1:
+            out.append(("lengths", tight_spade(ns, per_set=5, prefix=d, seed=5), 1,
+                        {"lengths": [n + 1 for n in ns]}))
+        else:  # 64 < itemsets <= 128 in the longest sequence
+            out.append(("lengths", tight_spade(ns, per_set=3, prefix=d, seed=5), 1,
+                        {"lengths": [n + 1 for n in ns]}))
+        n = 63  # a 64-entry run in [A1]
+        ps = 3 if w == 1 else 1  # per_set = 1: 65 itemsets, two mask words
+        for r in range(64, 513, 64):
+            for start in (r - 63, r - 1, r):
+                lead, pad = place(1, start, d)
+                db = tight_spade([n], per_set=ps, prefix=d, lead=lead, pad=pad, seed=start)
+                out.append(("L1-start%d" % start, db, 1, {"start": start, "length": 64}))
+                if w == 1:  # the same placement in the root class (no prefix: every filler run is one entry)
+                    db = tight_spade([64], per_set=ps, lead=start, seed=start)
+                    out.append(("L0-start%d" % start, db, 0, {"start": start, "length": 64}))
+        db = tight_spade([20, n], per_set=ps, prefix=d, lead=[3, 5], hub_last=True, seed=6)
+        out.append(("hub-last", db, 1, {"end_is_E": True, "length": 64}))
+        return out
+    return _cached(("lattice", w), make)
+
+
+def check_lattice_claim(db, level, claim, minsup=2):
+    """Assert that the DB has the geometry its case is named after; returns the geometry."""
+    g = geometry(db.rows, minsup)
+    if "lengths" in claim:
+        got = [hub_run(db, g, h, level)[1] for h in range(len(db.hub_rows))]
+        assert got == claim["lengths"], (got, claim)
+        return g
+    hub = len(db.hub_rows) - 1
+    s, n = hub_run(db, g, hub, level)
+    if "start" in claim:
+        assert s == claim["start"], (s, claim)
+    if "length" in claim:
+        assert n == claim["length"], (n, claim)
+    if claim.get("end_is_E"):
+        assert s + n == (g["E_class"][1] if level == 1 else g["E_root"])
+    return g
+
+
+def mask_width(db):
+    """u64 mask words of a SPADE DB: the smallest power of two covering the most
+    non-empty itemsets of one sequence."""
+    e = max(sum(1 for s in itemsets_of(r) if s) for r in db.rows)
+    w = 1
+    while w * 64 < e:
+        w *= 2
+    return w
+
+
+def rk_cases():
+    """Family 3, row-table sizes: (name, db, rows of the root batch, rows of the
+    first-level batch).  prefix = 1 and one hub of 5: the root batch has one
+    counter row per frequent item (F), the first-level batch one per member:
+    F - 1 members A1 -> x plus one per selected pattern."""
+    def make():
+        out = []
+        nsel = len(_selected_ranks(5))
+        for F in RK_SIZES + (FREQ_RECS_ROWS,):
+            for which, Fx in (("root", F), ("level1", F + 1 - nsel)):
+                db = tight_spade([5], per_set=2, prefix=1, filler=Fx - 6, seed=F)
+                out.append(("%s-%d" % (which, F), db, Fx, Fx - 1 + nsel))
+        return out
+    return _cached("rk", make)
+
+
+ONE_ROW_GROUP_F = (8192, 8193, 10923, 10924, 16384)
+
+
+def one_row_group_cases():
+    """(F, db): F frequent items whose root counter row (2 F counters) takes more than half
+    of a rank group's 32,768 counters from F = 8,193 on, so the ordered root F2 holds one row
+    per group; 16,384 is the last F it takes (8,192: the last with two rows per group).  10,923 is
+    the last F of the unordered layout (its first row has 1 + 3 (F - 1) counters), 10,924 the first
+    that takes the ordered one by default."""
+    return _cached("one_row", lambda: [(F, tight_spade([5], per_set=2, prefix=1, filler=F - 6, seed=7))
+                                       for F in ONE_ROW_GROUP_F])
+
+
+def mask_cases():
+    return _cached("mask", lambda: [(E, W, wide_mask_db(E, shared_last=E != 4096)) for E, W in zip(MASK_E, MASK_W)])
+
+
+def big_row_cases():
+    return _cached("bigrow", lambda: [(n, big_row_db(n)) for n in (65535, 65536)])
+
+
+def tsr_long_cases():
+    """(name, db, k, minconf): tsr_long_rows at TSR_T with the first, middle and
+    last tail item tight, and a mixed DB with short sequences between the long ones
+    (there 1 -> 2 has confidence 8 / 32)."""
+    def make():
+        out = [("T%d" % T, tsr_long_rows(T, tight=(0, T // 2, T - 1)), 5, 0.5) for T in TSR_T]
+        out.append(("mixed", tsr_long_rows(4200, tight=(0, 2100, 4199), short_between=3), 5, 0.2))
+        return out
+    return _cached("tsr_long", make)
+
+
+def tsr_sid_cases():
+    return _cached("tsr_sid", lambda: [(N, tsr_sid_edges(N)) for N in TSR_N])
+
+
+def k0_cases():
+    """(name, rows, modes, device build expected) for the K0 image comparison."""
+    def make():
+        rng = random.Random(8)
+        out = []
+
+        def rnd(L, items=40):
+            return [rng.choice((-1, -1, -2)) if rng.random() < 0.3 else rng.randint(1, items) for _ in range(L)]
+        # token counts on the wave / block / host switches; a short closed row beside each
+        for L in (0, 1, 63, 64, 65, 8191, 8192, 8193):
+            rows = [rnd(L)[:max(L - 1, 0)] + ([-1] if L else []), [1, 2, -1, 3, -1, -2], rnd(30)]
+            out.append(("tokens-%d" % L, rows, ("spade", "tsr"), L <= 8192))
+        one = [5, -1] * 4096  # one item in all 4,096 itemsets of an 8,192-token row
+        out.append(("one-item-4096-sets", [one, [5, -1, 6, -1]], ("spade", "tsr"), True))
+        rep = [t for k in range(4096) for t in (1 + rng.randrange(16), -1 if k % 3 else -2)]
+        rep[-1] = -1
+        out.append(("16-items-repeated", [rep, [1, -1]], ("spade", "tsr"), True))
+        for rng_items, ok in ((2 ** 19 - 1, True), (2 ** 19, True), (2 ** 19 + 1, True), (2 ** 27, True),
+                              (2 ** 27 + 1, False)):
+            lo, hi = 7, 7 + rng_items - 1  # hi - lo + 1 values in the range, three of them present
+            mid = lo + rng_items // 2
+            rows = [[hi, -1, lo, mid, -1, lo, -1], [mid, -1, hi, -1], [lo, hi, -1]]
+            out.append(("range-%d" % rng_items, rows, ("spade", "tsr"), ok))
+        for E, ok in ((4096, True), (4097, False)):
+            row = [t for k in range(E) for t in (1 + k % 50, -1)]
+            out.append(("eids-%d" % E, [row, [1, -1, 2, -1]], ("spade",), ok))
+        return out
+    return _cached("k0", make)
