@@ -13,7 +13,10 @@ TEST INFRASTRUCTURE ONLY (plain Python, no GPU).  Two ideas:
 Families: `tight_spade` (hub sequences), `wide_mask_db` (one sequence of E
 itemsets), `big_row_db` (one DB row of n entries), `tsr_long_rows`,
 `tsr_sid_edges`, and `k0_image`, the DB image by definition from the token
-rules (SPADE.scala:53-106, :151-210; TSR.scala:52-94, :109-143).
+rules (SPADE.scala:53-106, :151-210; TSR.scala:52-94, :109-143); and the TSR
+families placed on the expansion kernels' constants (`tsr_constants`, read
+from tsr_engine.hip): `tsr_probe_edges`, `tsr_kid_edges`, `tsr_chain`,
+`tsr_pair_edges`.
 """
 import os
 import random
@@ -726,3 +729,350 @@ def k0_cases():
             out.append(("eids-%d" % E, [row, [1, -1, 2, -1]], ("spade",), ok))
         return out
     return _cached("k0", make)
+
+
+# ---------------------------------------------------------------- TSR on the expansion kernels' constants
+TSR_SRC = os.path.join(ROOT, "spark-fsm_amd", "csrc", "tsr_engine.hip")
+
+
+def tsr_constants():
+    """The constants of tsr_engine.hip the TSR families below are placed on, read from the source
+    itself (every one must be found), plus what the kernels derive from them:
+    group       sids per rank-directory entry (bm_rank: one 16-byte group of four 32-bit words)
+    wave_groups sids per wave of k_rank_dir (64 groups), rank_round per block round (kBlock groups)
+    exp_win     domain rows per k_exp_rows window (kExpWin = 2 kXBlock)
+    reduce_range kids per k_expand_reduce block (ceil(kPassKids / kCollectBlocks))
+    dl_round    bitmap words (AND branch) or list sids (list branch) per k_dl block round
+    pair_batch0 items of the pair phase's first batch (doubling up to 4,096)"""
+    def make():
+        with open(TSR_SRC) as f:
+            src = f.read()
+        out = {}
+        m = re.search(r"^#define\s+FSM_TSR_XBLOCK\s+(\d+)\b", src, re.M)
+        assert m, "no #define FSM_TSR_XBLOCK in tsr_engine.hip"
+        out["FSM_TSR_XBLOCK"] = int(m.group(1))
+        for name in ("kPassKids", "kCollectBlocks", "kDomThreads", "kBlock", "kDlUnroll", "kExpSpb", "kExpBatch",
+                     "kExpBatchWide", "kWideMinsup"):
+            m = re.search(r"^constexpr\s+(?:int|uint32_t)\s+%s\s*=\s*(\d+)\s*;" % name, src, re.M)
+            assert m, "no constexpr %s in tsr_engine.hip" % name
+            out[name] = int(m.group(1))
+        assert re.search(r"kExpWin\s*=\s*2\s*\*\s*kXBlock\s*;", src), "kExpWin is no longer 2 * kXBlock"
+        assert re.search(r"g\s*=\s*sid\s*>>\s*7\b", src), "bm_rank no longer takes 128-sid groups"
+        m = re.search(r"uint32_t\s+nb_items\s*=\s*(\d+)\s*;", src)
+        assert m, "no first pair batch size (nb_items) in tsr_engine.hip"
+        out["pair_batch0"] = int(m.group(1))
+        out["group"] = 128
+        out["wave_groups"] = 64 * out["group"]
+        out["rank_round"] = out["kBlock"] * out["group"]
+        out["exp_win"] = 2 * out["FSM_TSR_XBLOCK"]
+        out["reduce_range"] = -(-out["kPassKids"] // out["kCollectBlocks"])
+        out["dl_round"] = out["kBlock"] * out["kDlUnroll"]
+        return out
+    return dict(_cached("tsr_constants", make))
+
+
+def probe_edges():
+    """Sids one before and on the group, wave-of-groups, round and two-round edges of k_rank_dir
+    (127, 128, 8,191, 8,192, 32,767, 32,768, 65,535, 65,536 with 256 threads per block)."""
+    c = tsr_constants()
+    return tuple(s for e in (c["group"], c["wave_groups"], c["rank_round"], 2 * c["rank_round"]) for s in (e - 1, e))
+
+
+def window_edges():
+    """Sids one before and on the first two window ends of k_exp_rows (1,023, 1,024, 2,047, 2,048)."""
+    w = tsr_constants()["exp_win"]
+    return (w - 1, w, 2 * w - 1, 2 * w)
+
+
+def bitmap_words(N):
+    """Words of a sid bitmap: whole 128-sid groups."""
+    return (N + 127) // 128 * 4
+
+
+def tsr_probe_edges(N, extra=(), edges=None, dl=None, sup3=None):
+    """Two item triples, (1, 2, 3) and (11, 12, 13); every sequence holds all six items in three
+    itemsets.  A triple (a, b, c) HOLDS in a row <{a}, {c}, {b}> and FAILS in <{b}, {c}, {a}>; the
+    two triples share the itemsets of a row (<{a, a'}, {c, c'}, {b, b'}>, each triple in its own
+    order).  A fail row has the same items, so it is in every domain and is probed like a hold
+    row, with first / last values that make the rule fail.
+
+    Triple 1 holds exactly at the `deciding` sids: 0, 1, N - 1, every sid of `edges` (default
+    probe_edges()) below N, and `extra`: m = len(deciding) rows, so a -> b, a -> c, c -> b,
+    a -> {b, c}, {a, c} -> b and the rules that add 13 (present in every row's middle itemset)
+    have support exactly m.  Triple 2 holds at m - 1 other sids spread between them (`second`):
+    its rules have support m - 1.  The reversed rules (b -> a ...) have support N - m and
+    N - m + 1.  A rank that is off by one at a deciding row or at a fail row reads another row's
+    first / last and moves a count across the line between m and m - 1.
+
+    dl = "and":  item 3 is removed from the fail rows at and beside the edge sids (`removed`),
+                 so |sids({1, 3})| = N - len(removed), counted by k_dl's AND branch
+                 (sup(3) >= bitmap words);
+    dl = "list": item 3 stays in the hold rows of both triples, in those fail rows and in evenly
+                 spread others, sup3 sequences in all (default: bitmap words - 2, the longest list the
+                 list branch takes), and is removed everywhere else."""
+    edges = probe_edges() if edges is None else tuple(edges)
+    deciding = sorted({0, 1, N - 1} | {e for e in edges if e < N} | {e for e in extra if 0 <= e < N})
+    m = len(deciding)
+    dset = set(deciding)
+    beside = sorted({s for e in edges for s in (e - 2, e - 1, e, e + 1) if 0 <= s < N} - dset)
+    others = [s for s in range(2, N) if s not in dset and s not in beside]
+    step = max(1, len(others) // (m - 1))
+    second = others[::step][:m - 1]
+    assert len(second) == m - 1, (N, m)
+    sset = set(second)
+    if dl is None:
+        removed = set()
+    elif dl == "and":
+        removed = set(beside)
+        assert N - len(removed) >= bitmap_words(N)
+    else:
+        assert dl == "list"
+        n3 = bitmap_words(N) - 2 if sup3 is None else sup3
+        keep = list(deciding) + second + beside
+        rest = [s for s in others if s not in sset]
+        need = n3 - len(keep)
+        assert 0 < need <= len(rest), (N, n3)
+        keep += rest[::max(1, len(rest) // need)][:need]
+        assert len(keep) == n3 < bitmap_words(N) or sup3 is not None
+        removed = set(range(N)) - set(keep)
+    rows = []
+    for s in range(N):
+        h1, h2 = s in dset, s in sset
+        head = [1 if h1 else 2, 11 if h2 else 12]
+        tail = [2 if h1 else 1, 12 if h2 else 11]
+        rows.append(_row([head, [13] if s in removed else [3, 13], tail]))
+    db = EdgeDB(rows, "tsr-probe-%d%s%s" % (N, "-" + dl if dl else "", "+%d" % len(extra) if extra else ""))
+    db.N, db.m, db.deciding, db.second, db.removed, db.dl, db.edges = N, m, deciding, second, sorted(removed), dl, edges
+    db.minconf = 0.0
+    return db
+
+
+def item_sid_masks(db):
+    """{item: bool array over the sids} by definition."""
+    lens = np.diff(db.seq_off)
+    seq_of = np.repeat(np.arange(len(db.rows)), lens)
+    out = {}
+    for it in np.unique(db.tokens[db.tokens >= 0]):
+        mk = np.zeros(len(db.rows), dtype=bool)
+        mk[seq_of[db.tokens == it]] = True
+        out[int(it)] = mk
+    return out
+
+
+def tsr_domain_sum(db, rules):
+    """Sum over the rules of |sids(X u Y)| (the sequences holding every item of the rule, in any
+    order): what the expansions of exactly these rules walk as their domains."""
+    masks = item_sid_masks(db)
+    memo, tot = {}, 0
+    for r in rules:
+        key = tuple(sorted(r[0] + r[1]))
+        if key not in memo:
+            mk = masks[key[0]].copy()
+            for it in key[1:]:
+                mk &= masks[it]
+            memo[key] = int(mk.sum())
+        tot += memo[key]
+    return tot
+
+
+def tsr_kid_edges(T, low, tight_kids):
+    """tsr_long_rows(T) with every item value raised by `low`, plus (low > 0) eight filler
+    sequences of ONE itemset holding the items 1 .. low: the fillers have support 8 like every
+    other item (all are kept whatever the pair phase's threshold: K = low + 3 + T kids) and a
+    single itemset yields no rule.  Dense kids: fillers 0 .. low - 1, the core items low,
+    low + 1, low + 2, tail item j low + 3 + j.  `tight_kids` names the tight tail items by kid.
+    lo_abs = min(max X, max Y) + 1 of the five core rules is low + 1 or low + 2."""
+    tight = sorted(k - (low + 3) for k in tight_kids)
+    assert all(0 <= j < T for j in tight), (T, low, tight_kids)
+    base = tsr_long_rows(T, tight=tight)
+    rows = [[t + low if t > 0 else t for t in r] for r in base.rows]
+    if low:
+        rows += [_row([list(range(1, low + 1))]) for _ in range(8)]
+    db = EdgeDB(rows, "tsr-kids-%d-low%d" % (T, low))
+    db.T, db.N, db.low, db.tight, db.tight_kids, db.K = T, 8, low, tight, sorted(tight_kids), low + 3 + T
+    db.core = (low + 1, low + 2, low + 3)
+    db.tail_item = lambda j: low + 10 + j
+    db.minconf = 0.5
+    return db
+
+
+def kid_lo_abs(db, X, Y):
+    """lo_abs of a rule by definition: the dense rank (kid, every item kept) of
+    min(max X, max Y), plus one."""
+    vals = sorted({t for r in db.rows for t in r if t >= 0})
+    return vals.index(min(max(X), max(Y))) + 1
+
+
+def tsr_chain(n, copies):
+    """`copies` sequences <{1}, {2}, ..., {n}>, one that lacks item n, and two reversed ones
+    (first and last sid), which are in every domain and hold no forward rule.  The forward rules
+    X -> Y (max X < min Y) have support copies + 1 without item n and copies with it, the
+    reversed ones 2; |X u Y| goes up to n."""
+    fwd = _row([[i] for i in range(1, n + 1)])
+    rev = _row([[i] for i in range(n, 0, -1)])
+    h = copies // 2
+    rows = [list(rev)] + [list(fwd) for _ in range(h)] + [_row([[i] for i in range(1, n)])]
+    rows += [list(fwd) for _ in range(copies - h)] + [list(rev)]
+    db = EdgeDB(rows, "tsr-chain-%d-%d" % (n, copies))
+    db.n, db.copies, db.minconf = n, copies, 0.0
+    return db
+
+
+def pair_batch_starts(U):
+    """First dense item id of every pair-phase batch after the first (16, 48, 112, 240, 496 ...:
+    batches double from pair_batch0 up to 4,096 items while their candidates stay few)."""
+    out, a, nb = [], 0, tsr_constants()["pair_batch0"]
+    while a + nb < U:
+        a += nb
+        out.append(a)
+        nb = min(2 * nb, 4096)
+    return out
+
+
+def tsr_pair_edges(U, m=4, starts=None, offs=(1, 63, 64, 65), seed=9):
+    """U items (values 1 .. U, dense id = value - 1), every one in m single-item sequences of its
+    own (support >= m: all are kept).  The only rules are the planted pairs i -> j and j -> i:
+    i (dense) the last item of a pair-phase batch and the first of the next (`starts`, default
+    pair_batch_starts(U)), j in {i + 1, i + 63, i + 64, i + 65, U - 1} (k_pairs_compact walks j
+    from i + 1 in steps of 64 lanes).  Pair p has i -> j in a sequences <{i}, {j}> and j -> i in
+    b sequences <{j}, {i}>, (a, b) cycling through (m, m - 1), (m - 1, m), (m, m),
+    (m - 1, m - 1).  The sequences are shuffled (seeded), so every sid slice holds a mixture."""
+    starts = pair_batch_starts(U) if starts is None else list(starts)
+    ids = sorted({e - 1 for e in starts} | set(starts))
+    pairs = []
+    for i in ids:
+        for j in [i + o for o in offs] + [U - 1]:
+            if i < j < U and (i, j) not in pairs:
+                pairs.append((i, j))
+    rows, planted = [], {}
+    for p, (i, j) in enumerate(pairs):
+        a, b = ((m, m - 1), (m - 1, m), (m, m), (m - 1, m - 1))[p % 4]
+        rows += [_row([[i + 1], [j + 1]]) for _ in range(a)] + [_row([[j + 1], [i + 1]]) for _ in range(b)]
+        planted[((i + 1,), (j + 1,))] = a
+        planted[((j + 1,), (i + 1,))] = b
+    rows += [_row([[d + 1]]) for d in range(U) for _ in range(m)]
+    random.Random(seed).shuffle(rows)
+    db = EdgeDB(rows, "tsr-pairs-%d" % U)
+    db.U, db.m, db.pairs, db.planted, db.starts, db.minconf = U, m, pairs, planted, starts, 0.0
+    return db
+
+
+# ---- case tables of tests/test_tsr_edges_gpu.py (tests/test_edge_dbs.py proves them on the CPU)
+def tsr_all_rules(db, t=1):
+    """oracle.tsr_all of a DB at threshold t and the DB's minconf, once per process."""
+    def make():
+        from oracle import oracle
+        return oracle.tsr_all(db.seq_off, db.tokens, t, db.minconf)["rules"]
+    return _cached(("tsr_all", id(db), t), make)
+
+
+def tsr_modes(db):
+    """[(mode, k, final minsup)]: exhaustive (k = every valid rule: final minsup 1) and tight
+    (k = the rules with support >= m: the rules planted at m - 1 are left out)."""
+    rules = tsr_all_rules(db)
+    return [("exhaustive", len(rules), 1), ("tight", sum(1 for r in rules if r[2] >= db.m), db.m)]
+
+
+def probe_sizes():
+    return tuple(e + 1 for e in probe_edges()[1::2])
+
+
+def shard_cuts(N):
+    """The sids N r / R - 1 and N r / R at which the sharded pair phase cuts (R = 2, 3)."""
+    return tuple(sorted({s for R in (2, 3) for r in range(1, R) for s in (N * r // R - 1, N * r // R)}))
+
+
+def tsr_probe_cases():
+    """{name: db}: family A.  N one past each rank-directory edge, and one group past the round
+    edge; the k_dl variants (item 3 removed) at N = 8,193 and 65,537; and the DBs whose deciding
+    sids include the shard cuts."""
+    def make():
+        sizes = probe_sizes()
+        out = {"N%d" % N: tsr_probe_edges(N) for N in sizes}
+        # one group past a block round of k_rank_dir: with N = 32,769 the only sid of the second round is a
+        # hold row whose rank without the carry is sid 0's, a hold row too; here the fail rows 32,769 ..
+        # 32,896 would read the entries of the sids 1 .. 128, three of them hold rows
+        c = tsr_constants()
+        N = c["rank_round"] + c["group"] + 1
+        out["N%d" % N] = tsr_probe_edges(N)
+        for N in (sizes[1], sizes[3]):
+            for dl in ("and", "list"):
+                out["N%d-dl-%s" % (N, dl)] = tsr_probe_edges(N, dl=dl)
+            out["N%d-cuts" % N] = tsr_probe_edges(N, extra=shard_cuts(N))
+        return out
+    return _cached("tsr_probe", make)
+
+
+def tsr_window_cases():
+    """{name: db}: family B.  N on 1,023 .. 2,049 (domains of one, two and three windows, the
+    last of 1,023, 1,024 or one row), and three DBs of 1,030 sequences whose big rules (2 -> 1:
+    the N - m fail rows of triple 1) keep exactly 1,025, 1,024 and 1,023 rows for their children."""
+    def make():
+        w = tsr_constants()["exp_win"]
+        we = window_edges()
+        out = {"N%d" % N: tsr_probe_edges(N, edges=we) for N in (w - 1, w, w + 1, 2 * w, 2 * w + 1)}
+        for n_extra in (0, 1, 2):
+            db = tsr_probe_edges(w + 6, extra=(500, 700)[:n_extra], edges=we)
+            out["plist%d" % (db.N - db.m)] = db
+        return out
+    return _cached("tsr_window", make)
+
+
+def tsr_kid_cases():
+    """{name: db}: family C.  low on kPassKids - 3 .. kPassKids - 1 with T = 4,200, and low = 0
+    with T = 8,300; the tight tail kids on the pass edges, the first and last tail kid and the
+    reduce-range edges of pass 1."""
+    def make():
+        c = tsr_constants()
+        P, q = c["kPassKids"], c["reduce_range"]
+        out = {}
+        for low in (P - 3, P - 2, P - 1):
+            T = 4200
+            first, last = low + 3, low + 3 + T - 1
+            kids = {k for k in (P - 1, P, P + 1) if k >= first} | {first, last, P + q - 1, P + q}
+            out["low%d" % low] = tsr_kid_edges(T, low, sorted(kids))
+        out["low0"] = tsr_kid_edges(8300, 0, [q - 1, q, P - 1, P, P + 1, 2 * P - 1, 2 * P])
+        return out
+    return _cached("tsr_kid", make)
+
+
+def tsr_kid_modes(db):
+    """[(mode, k, final minsup)] of a family C DB: k = 5 (the core rules, final minsup 8: a tight kid
+    counted 8 adds a rule), and k = the two-item rules of support >= 7, which ends the pair phase at
+    minsup 7 before the tail x tail pairs: the answer then holds rules of every tight tail item at
+    exactly 7 (a tight kid counted 6 loses them).  A k that keeps the threshold lower costs the top-k
+    restatement tens of seconds per DB."""
+    k7 = sum(1 for r in tsr_all_rules(db, 7) if len(r[0]) + len(r[1]) == 2)
+    return [("k5", 5, 8), ("pairs7", k7, 7)]
+
+
+def tsr_chain_cases():
+    """{name: (db, [(mode, k, final minsup)])}: family D.  n = 5, 9, 10 exhaustively, and n = 10
+    with copies = kWideMinsup - 1 (forward rules at kWideMinsup, those with item n one below) at
+    the two k that end the pair phase at kWideMinsup (k = the two-item rules at that support:
+    wide batches) and at kWideMinsup - 1 (one more: the k-th two-item rule holds item n; the
+    expansions then raise the minsup to kWideMinsup again).  Rules that tie the final minsup
+    stay, so both answers are every rule at or above kWideMinsup."""
+    def make():
+        W = tsr_constants()["kWideMinsup"]
+        out = {}
+        for n in (5, 9, 10):
+            db = tsr_chain(n, 6)
+            db.m = 6
+            out["n%d" % n] = (db, tsr_modes(db))
+        db = tsr_chain(10, W - 1)
+        at_w = sum(1 for r in tsr_all_rules(db) if len(r[0]) + len(r[1]) == 2 and r[2] >= W)
+        out["n10-wide"] = (db, [("pairs-end-%d" % W, at_w, W), ("pairs-end-%d" % (W - 1), at_w + 1, W)])
+        return out
+    return _cached("tsr_chain", make)
+
+
+def pair_phase_threshold(rules, k):
+    """The minsup the pair phase ends at: the k-th largest support among the two-item rules
+    (1 while fewer than k are known)."""
+    sups = sorted((r[2] for r in rules if len(r[0]) + len(r[1]) == 2), reverse=True)
+    return sups[k - 1] if len(sups) >= k else 1
+
+
+def tsr_pair_case():
+    return _cached("tsr_pair", lambda: tsr_pair_edges(600))

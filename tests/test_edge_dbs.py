@@ -1,6 +1,6 @@
 """CPU tests of tests/edge_dbs.py: the threshold-tight families mean what they
-claim, so tests/test_edges_gpu.py is sensitive to a count that is off by one.
-No GPU.
+claim, so tests/test_edges_gpu.py and tests/test_tsr_edges_gpu.py are sensitive
+to a count that is off by one.  No GPU.
 
 For every family: at its small sizes the oracle's answer against the
 definitional enumerator (oracle/brute.py); at every size the GPU tests use,
@@ -214,3 +214,265 @@ def test_k0_image_small_known_answer():
     for name, rows, modes, dev in E.k0_cases():
         if name.startswith("eids-"):
             assert E.k0_image(rows, "spade")["mask_words"] == (64 if dev else 128)
+
+
+# ------------------------------------------------------------ TSR families on the expansion kernels' constants
+def rsup(db, X, Y):
+    return oracle.rule_support(db.seq_off, db.tokens, list(X), list(Y))
+
+
+def assert_modes(db, modes):
+    """oracle.tsr at each mode's k returns exactly the rules of tsr_all at or above the mode's
+    final minsup (every valid rule in exhaustive mode), and ends at that minsup."""
+    allr = E.tsr_all_rules(db)
+    for mode, k, final in modes:
+        o = oracle.tsr(db.records(), k, db.minconf)
+        assert o["final_minsup"] == final, (db.name, mode)
+        assert o["rules"] == [r for r in allr if r[2] >= final], (db.name, mode)
+
+
+def holds_at(db, X, Y):
+    """The sids where X => Y holds, from the rows by definition."""
+    out = []
+    for s, r in enumerate(db.rows):
+        first, last = {}, {}
+        for j, st in enumerate(E.itemsets_of(r)):
+            for it in st:
+                first.setdefault(it, j)
+                last[it] = j
+        if all(x in first for x in X) and all(y in last for y in Y) and \
+                max(first[x] for x in X) < min(last[y] for y in Y):
+            out.append(s)
+    return out
+
+
+def test_tsr_constants_found():
+    c = E.tsr_constants()
+    for key in ("FSM_TSR_XBLOCK", "kPassKids", "kCollectBlocks", "kDomThreads", "kBlock", "kDlUnroll", "kExpSpb",
+                "kExpBatch", "kExpBatchWide", "kWideMinsup", "pair_batch0"):
+        assert c[key] > 0, key
+    # the edge sids follow the constants: groups, a wave of groups, a block round and two of k_rank_dir; a
+    # block round of k_dl (words of 32 sids) ends where two rounds of k_rank_dir do
+    assert E.probe_edges() == tuple(s for e in (128, 64 * 128, c["kBlock"] * 128, c["kBlock"] * 256) for s in (e - 1, e))
+    assert c["dl_round"] * 32 in (c["rank_round"], 2 * c["rank_round"])
+    assert E.window_edges()[1] == 2 * c["FSM_TSR_XBLOCK"]
+
+
+@pytest.mark.parametrize("kw", [dict(N=12, edges=(5, 6)), dict(N=20, edges=(7, 8), dl="and"),
+                                dict(N=24, edges=(7, 8), extra=(15,), dl="list", sup3=16)], ids=str)
+def test_tsr_probe_edges_small_vs_brute(kw):
+    db = E.tsr_probe_edges(**kw)
+    recs = db.records()
+    valid = brute.brute_tsr_valid(recs, 0.0)
+    allr = E.tsr_all_rules(db)
+    assert {(x, y): (s, c) for x, y, s, c in allr} == valid
+    for mode, k, final in E.tsr_modes(db):
+        o = oracle.tsr(recs, k, 0.0)
+        brute.check_tsr(o["rules"], valid, k)
+        assert o["final_minsup"] == final and o["rules"] == [r for r in allr if r[2] >= final]
+    assert valid[((1,), (2,))][0] == db.m and valid[((11,), (12,))][0] == db.m - 1
+
+
+def test_tsr_kid_edges_small_vs_brute():
+    db = E.tsr_kid_edges(4, 2, [5, 8])
+    recs = db.records()
+    valid = brute.brute_tsr_valid(recs, 0.5)
+    o = oracle.tsr(recs, 5, 0.5)
+    brute.check_tsr(o["rules"], valid, 5)
+    assert o["final_minsup"] == 8 and len(o["rules"]) == 5
+    assert valid[((db.tail_item(0),), (db.core[1],))][0] == 7 and valid[((db.tail_item(3),), (db.core[2],))][0] == 7
+    assert {(x, y): (s, c) for x, y, s, c in E.tsr_all_rules(db, 7)} == {r: v for r, v in valid.items() if v[0] >= 7}
+
+
+@pytest.mark.parametrize("n,copies", [(3, 3), (4, 3), (5, 4)])
+def test_tsr_chain_small_vs_brute(n, copies):
+    db = E.tsr_chain(n, copies)
+    db.m = copies
+    recs = db.records()
+    valid = brute.brute_tsr_valid(recs, 0.0)
+    allr = E.tsr_all_rules(db)
+    assert {(x, y): (s, c) for x, y, s, c in allr} == valid
+    for mode, k, final in E.tsr_modes(db):
+        o = oracle.tsr(recs, k, 0.0)
+        brute.check_tsr(o["rules"], valid, k)
+        assert o["final_minsup"] == final and o["rules"] == [r for r in allr if r[2] >= final]
+
+
+def test_tsr_pair_edges_small_vs_brute():
+    db = E.tsr_pair_edges(9, m=2, starts=(4,), offs=(1, 2, 3))
+    recs = db.records()
+    valid = brute.brute_tsr_valid(recs, 0.0)
+    assert {r: v[0] for r, v in valid.items()} == db.planted
+    for mode, k, final in E.tsr_modes(db):
+        o = oracle.tsr(recs, k, 0.0)
+        brute.check_tsr(o["rules"], valid, k)
+        assert o["final_minsup"] == final
+
+
+@pytest.mark.parametrize("name", list(E.tsr_probe_cases()) + ["B-" + n for n in E.tsr_window_cases()])
+def test_tsr_probe_and_window_cases(name):
+    """Families A and B at the sizes the GPU tests use: the two modes, the planted rules at
+    exactly m and m - 1, the deciding sids on the edges, the k_dl variants' denominators, the
+    domain (every sid) in windows, and the kept rows of the big rules."""
+    c = E.tsr_constants()
+    fam_b = name.startswith("B-")
+    db = E.tsr_window_cases()[name[2:]] if fam_b else E.tsr_probe_cases()[name]
+    N, m = db.N, db.m
+    modes = E.tsr_modes(db)
+    assert_modes(db, modes)
+    allr = E.tsr_all_rules(db)
+    at_m = [r for r in allr if r[2] == m]
+    assert at_m and len(at_m) == len([r for r in allr if r[2] == m - 1])
+    assert modes[1][1] == len([r for r in allr if r[2] >= m]) < modes[0][1] == len(allr)
+    # triple 1 holds exactly at the deciding sids, triple 2 at one fewer, spread between them
+    assert holds_at(db, [1], [2]) == db.deciding and len(db.deciding) == m
+    assert holds_at(db, [11], [12]) == sorted(db.second) and len(db.second) == m - 1
+    assert not set(db.second) & set(db.deciding) and db.second[0] > db.deciding[1] and db.second[-1] < N - 1
+    assert {0, 1, N - 1} | {e for e in db.edges if e < N} <= set(db.deciding)
+    if not fam_b:  # N is one past an edge, or one group past the round edge
+        assert N - 1 in db.edges or N - 1 == c["rank_round"] + c["group"]
+    n3 = N - len(db.removed)
+    for X, Y, s in (([1], [2], m), ([1], [3], m), ([3], [2], m), ([1, 3], [2], m), ([1], [2, 3], m), ([1], [13], m),
+                    ([11], [12], m - 1), ([11], [13], m - 1), ([11, 13], [12], m - 1), ([3], [12], m - 1)):
+        assert rsup(db, X, Y)[0] == s, (X, Y)
+    assert rsup(db, [2], [1]) == (N - m, N) and rsup(db, [12], [11]) == (N - m + 1, N)
+    # every sequence holds the five items besides 3: every domain without item 3 is all N sids
+    masks = E.item_sid_masks(db)
+    assert all(masks[i].all() for i in (1, 2, 11, 12, 13)) and int(masks[3].sum()) == n3
+    assert E.tsr_domain_sum(db, allr) == sum(n3 if 3 in r[0] + r[1] else N for r in allr)
+    if db.dl:
+        # |sids({1, 3})| is not N, and the confidence of {1, 3} => 2 is m over it: it depends on the sids
+        # item 3 was removed from
+        assert rsup(db, [1, 3], [2]) == (m, n3) and n3 != N
+        conf = [r[3] for r in allr if r[:2] == ((1, 3), (2,))]
+        assert conf == [m / n3] and conf != [m / N]
+        assert set(db.removed).isdisjoint(db.deciding)
+        NW = E.bitmap_words(N)
+        if db.dl == "and":
+            # sup(3) >= bitmap words: the AND branch; the removed sids lie within two of an edge, on both
+            # sides of the word edges, and (N = 65,537) the bitmap is one word longer than a block round
+            assert n3 >= NW and all(min(abs(s - e) for e in db.edges) <= 2 for s in db.removed)
+            assert {e - 2 for e in db.edges[::2] if e < N} <= set(db.removed)
+            assert {e + 1 for e in db.edges[1::2] if e + 1 < N - 1} <= set(db.removed)
+            assert NW > c["kBlock"] and (N < 65537 or NW > c["dl_round"])
+        else:
+            # sup(3) < bitmap words: the list branch, over more than one thread round (and, at N = 65,537,
+            # two sids more than one block round of kBlock kDlUnroll)
+            assert NW - 2 == n3 > c["kBlock"] and (N < 65537 or n3 == c["dl_round"] + 2)
+    if name.endswith("-cuts"):
+        assert set(E.shard_cuts(N)) <= set(db.deciding) and len(E.shard_cuts(N)) >= 5
+    if fam_b:
+        w = c["exp_win"]
+        # at supports of a few units a slot gets one block (2 sup <= kExpSpb): its domain, all N sids, is
+        # ceil(N / w) windows; the big rules keep N - m (N - m + 1) rows for their children
+        assert 2 * m <= c["kExpSpb"] and (N - m) > c["kExpSpb"]
+        if name[2:].startswith("N"):
+            assert (N, -(-N // w), (N - 1) % w + 1) in ((w - 1, 1, w - 1), (w, 1, w), (w + 1, 2, 1), (2 * w, 2, w),
+                                                        (2 * w + 1, 3, 1))
+        else:
+            assert N - m == int(name[7:]) and len(holds_at(db, [2], [1])) == N - m
+
+
+def test_tsr_window_cases_cover_the_parent_list_edges():
+    w = E.tsr_constants()["exp_win"]
+    cases = E.tsr_window_cases()
+    assert {db.N for db in cases.values()} >= {w - 1, w, w + 1, 2 * w, 2 * w + 1}
+    assert {db.N - db.m for n, db in cases.items() if n.startswith("plist")} == {w - 1, w, w + 1}
+
+
+@pytest.mark.parametrize("name", list(E.tsr_kid_cases()))
+def test_tsr_kid_cases_placed(name):
+    """Family C: K = low + 3 + T kids, all of support 8; the tight tail items sit on the kids the
+    case names (dense rank of the item value), their rules are at 7 and the core rules at 8; lo_abs
+    of the core rules covers kPassKids - 1, kPassKids and kPassKids + 1 over the three lows."""
+    c = E.tsr_constants()
+    P, q = c["kPassKids"], c["reduce_range"]
+    for db in [E.tsr_kid_cases()[name]]:
+        vals = sorted({t for r in db.rows for t in r if t >= 0})
+        sup = {}
+        for r in db.rows:
+            for t in set(r):
+                if t >= 0:
+                    sup[t] = sup.get(t, 0) + 1
+        assert len(vals) == db.K == db.low + 3 + db.T and set(sup.values()) == {8}, name
+        assert [vals.index(v) for v in db.core] == [db.low, db.low + 1, db.low + 2]
+        a7 = E.tsr_all_rules(db, 7)
+        o = oracle.tsr(db.records(), 5, 0.5)
+        assert o["final_minsup"] == 8 and o["rules"] == [r for r in a7 if r[2] >= 8] and len(o["rules"]) == 5, name
+        tight_rules = [r for r in a7 if r[2] == 7]
+        assert {r[2] for r in a7} == {7, 8}
+        for j, kid in zip(db.tight, db.tight_kids):
+            t = db.tail_item(j)
+            assert vals.index(t) == kid, name
+            for y in db.core[1:]:
+                assert rsup(db, [t], [y]) == (7, 8) and ((t,), (y,), 7, 7 / 8) in tight_rules
+        assert {x for r in tight_rules for x in r[0] + r[1]} - set(db.core) == {db.tail_item(j) for j in db.tight}
+        for j in (1, db.T // 2 + 1, db.T - 2):
+            if j not in db.tight:
+                assert rsup(db, [db.tail_item(j)], [db.core[1]])[0] == 4
+        # the second mode: the pair phase ends at 7, and the answer keeps rules of every tight item at 7
+        (_, k5, f5), (_, k7, f7) = E.tsr_kid_modes(db)
+        assert (k5, f5, f7) == (5, 8, 7) and E.pair_phase_threshold(a7, k7) == 7 and E.pair_phase_threshold(a7, k7 - 1) == 7
+        o7 = oracle.tsr(db.records(), k7, 0.5)
+        assert o7["final_minsup"] == 7 and set(o7["rules"]) <= set(a7) and set(o["rules"]) <= set(o7["rules"])
+        for j in db.tight:
+            assert any(db.tail_item(j) in r[0] + r[1] and r[2] == 7 for r in o7["rules"]), (name, j)
+        los = {E.kid_lo_abs(db, r[0], r[1]) for r in o["rules"]}
+        assert los == {db.low + 1, db.low + 2}, name
+        if db.low:
+            first, last = db.low + 3, db.K - 1
+            assert {first, last, P + q - 1, P + q} | {k for k in (P - 1, P, P + 1) if k >= first} == set(db.tight_kids)
+            assert len(db.rows) == 16 and all(len(E.itemsets_of(r)) == 1 for r in db.rows[8:])
+            assert -(-db.K // P) == 3  # three kid passes; the fillers end in the last kids of pass 0
+        else:
+            assert db.tight_kids == [q - 1, q, P - 1, P, P + 1, 2 * P - 1, 2 * P] and db.K > 2 * P
+
+
+def test_tsr_kid_cases_cover_the_pass_start():
+    P = E.tsr_constants()["kPassKids"]
+    lows = {db.low for db in E.tsr_kid_cases().values() if db.low}
+    assert lows == {P - 3, P - 2, P - 1}  # lo_abs = low + 1, low + 2 (proved per DB above)
+    assert {lo for low in lows for lo in (low + 1, low + 2)} >= {P - 1, P, P + 1}
+
+
+def test_tsr_chain_cases_placed():
+    """Family D: rules up to |X u Y| = n (4 / 5 and 8 / 9 items: DomProbe's rounds of 4, k_exp_domain's of 8),
+    more than 20 full launches in exhaustive mode at n = 10, and the pair-phase thresholds of the wide DB."""
+    c = E.tsr_constants()
+    W = c["kWideMinsup"]
+    sizes = set()
+    for name, (db, modes) in E.tsr_chain_cases().items():
+        assert_modes(db, modes)
+        allr = E.tsr_all_rules(db)
+        sizes |= {len(r[0]) + len(r[1]) for r in allr}
+        assert max(len(r[0]) + len(r[1]) for r in allr) == db.n
+        assert rsup(db, [1], [2])[0] == db.copies + 1 and rsup(db, [1], [db.n])[0] == db.copies
+        assert rsup(db, [2], [1])[0] == 2
+        if name == "n10":
+            assert modes[0][1] > 20 * c["kExpBatch"]
+        if name == "n10-wide":
+            (_, k_w, f_w), (_, k_n, f_n) = modes
+            assert E.pair_phase_threshold(allr, k_w) == W and E.pair_phase_threshold(allr, k_n) == W - 1
+            assert f_w == f_n == W and db.copies + 1 == W
+        else:
+            assert all(E.pair_phase_threshold(allr, k) == 1 for _, k, _ in modes)
+    assert {4, 5, 8, 9, 10} <= sizes
+
+
+def test_tsr_pair_case_placed():
+    """Family E: the planted pairs are the only rules, at exactly m and m - 1; i on the last item of a batch
+    and the first of the next, j one, 63, 64 and 65 past it and the last item."""
+    c = E.tsr_constants()
+    db = E.tsr_pair_case()
+    assert db.starts == [16, 48, 112, 240, 496] and c["pair_batch0"] == 16
+    allr = E.tsr_all_rules(db)
+    assert {r[:2]: r[2] for r in allr} == db.planted and set(db.planted.values()) == {db.m, db.m - 1}
+    for (X, Y), s in db.planted.items():
+        assert rsup(db, X, Y)[0] == s
+    assert_modes(db, E.tsr_modes(db))
+    masks = E.item_sid_masks(db)
+    assert sorted(masks) == list(range(1, db.U + 1)) and min(int(v.sum()) for v in masks.values()) >= db.m
+    ids = {i for i, _ in db.pairs}
+    assert ids == {15, 16, 47, 48, 111, 112, 239, 240, 495, 496}
+    for i in ids:
+        assert {j - i for a, j in db.pairs if a == i} == {1, 63, 64, 65, db.U - 1 - i}
