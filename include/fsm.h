@@ -173,7 +173,7 @@ typedef struct {
                                    positions before a later launch overwrote them */
 } fsm_stats;
 
-/* Per-kernel device time of the last fsm_*_mine call (HIP events on the
+/* Per-kernel device time of the last mine or filter call (HIP events on the
  * context's stream) with the kernel's algorithmic bytes: the
  * numbers bench.py's roofline is computed from. */
 typedef struct {
@@ -267,6 +267,24 @@ void fsm_token_db_free(fsm_token_db* t);
 
 int fsm_spade_mine(fsm_ctx* ctx, fsm_db* db, double support, int32_t dfs, fsm_patterns** out);
 void fsm_patterns_free(fsm_patterns* p);
+
+/* Condensed forms of a COMPLETE frequent set (what fsm_spade_mine returns), computed
+ * on the GPU:
+ *   FSM_KEEP_CLOSED   keeps the patterns no strict super-pattern of which has the same
+ *                     support (lossless: every support can be recovered from them)
+ *   FSM_KEEP_MAXIMAL  keeps the patterns no strict super-pattern of which is in the set
+ * *out is a new library-owned result (fsm_patterns_free) with the kept patterns in
+ * input order, total and minsup copied from `in`; kept_idx (NULL, or capacity in->n)
+ * receives their indexes in `in`, ascending.  `in` is borrowed, never modified, and may
+ * be caller-built; it is checked before any device work (offsets monotone, every pattern
+ * with an itemset, every itemset with an item, items strictly ascending inside an
+ * itemset: FSM_EINVAL otherwise).  Equal patterns are separate entries and do not drop
+ * each other.  n or n_items >= 2^32 - 2: FSM_ELIMIT.  A group context (ndevices > 1) runs
+ * the filter on its rank 0; with nranks > 1 each process filters its own complete result.
+ * fsm_stats is left as it is; the kernel statistics become the filter's (k_pf_*). */
+#define FSM_KEEP_CLOSED 1
+#define FSM_KEEP_MAXIMAL 2
+int fsm_patterns_filter(fsm_ctx* ctx, const fsm_patterns* in, int32_t keep, fsm_patterns** out, int64_t* kept_idx);
 
 int fsm_tsr_mine(fsm_ctx* ctx, fsm_db* db, int32_t k, double minconf, fsm_rules** out);
 void fsm_rules_free(fsm_rules* r);

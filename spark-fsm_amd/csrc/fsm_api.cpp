@@ -937,6 +937,26 @@ int fsm_tsr_mine(fsm_ctx* ctx, fsm_db* db, int32_t k, double minconf, fsm_rules*
     });
 }
 
+int fsm_patterns_filter(fsm_ctx* ctx, const fsm_patterns* in, int32_t keep, fsm_patterns** out, int64_t* kept_idx) {
+    if (!ctx || !in || !out) return fail(ctx, FSM_EINVAL, "null argument");
+    *out = nullptr;
+    if (keep != FSM_KEEP_CLOSED && keep != FSM_KEEP_MAXIMAL)
+        return fail(ctx, FSM_EINVAL, "keep must be FSM_KEEP_CLOSED(1) or FSM_KEEP_MAXIMAL(2) (got " + std::to_string(keep) + ")");
+    if (ctx->group) {
+        // rank 0's context, on the calling thread (its device is made current by the call);
+        // the group's statistics stay as they are, the kernel rows are the filter's
+        fsm::Group& g = *ctx->group;
+        if (!g.ready()) return group_finish(ctx, fsm::Group::kStalled);
+        fsm_ctx* r0 = g.ranks[0];
+        const int rc = fsm_patterns_filter(r0, in, keep, out, kept_idx);
+        ctx->err = r0->err;
+        if (rc == FSM_OK) ctx->kstats = r0->kstats;
+        return rc;
+    }
+    // (nranks > 1: every process filters its own complete result; no collectives)
+    return guarded(ctx, [&] { fsm::patterns_filter(ctx, in, keep, out, kept_idx); });
+}
+
 // (result arrays may be big host blocks: fsm::big_give frees malloc'ed ones, caches the others)
 void fsm_patterns_free(fsm_patterns* p) {
     if (!p) return;

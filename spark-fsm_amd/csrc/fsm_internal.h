@@ -251,7 +251,7 @@ struct fsm_ctx {
     bool result_root_only = false;  // a rank context of a group: only rank 0's result is returned
     int dev_share = 1;  // rank contexts of this group on the same device: default budgets are split
     std::shared_ptr<fsm::Pool> pool;  // device blocks of this context (see fsm::Pool)
-    std::vector<fsm_kernel_stat> kstats;  // of the last mine call
+    std::vector<fsm_kernel_stat> kstats;  // of the last mine or filter call
     std::unique_ptr<fsm::PinnedBuf> pin;  // small mapped readback slots, made on first use
     uint64_t* pinned_u64() {              // 16 u64 slots of pinned host memory
         if (!pin) pin = std::make_unique<fsm::PinnedBuf>(128);
@@ -324,6 +324,8 @@ void spade_mine(fsm_ctx* ctx, fsm_db* db, double support, fsm_patterns** out);
 void tsr_upload(fsm_ctx* ctx, fsm_db* db);
 void tsr_release(fsm_db* db);
 void tsr_mine(fsm_ctx* ctx, fsm_db* db, int32_t k, double minconf, fsm_rules** out);
+// closed / maximal filter of a complete frequent set (pattern_filter.hip); keep is validated by the caller
+void patterns_filter(fsm_ctx* ctx, const fsm_patterns* in, int32_t keep, fsm_patterns** out, int64_t* kept_idx);
 // FSM_HOST_PROF=<file>: SIGPROF sampling of the host side of a mine (host_prof.cpp)
 bool host_prof_start();
 void host_prof_stop();

@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("FSM_LIB_PATH") or os.path.join(HERE, "libfsm.so")  # 
 
 FSM_OK, FSM_EINVAL, FSM_EPARSE, FSM_EDEVICE, FSM_ENOMEM, FSM_ECOMM, FSM_ELIMIT = range(7)
 MODE_SPADE, MODE_TSR = 0, 1
+KEEP_CLOSED, KEEP_MAXIMAL = 1, 2  # FSM_KEEP_*
 MAX_DEVICES = 16  # FSM_MAX_DEVICES
 
 
@@ -142,7 +143,7 @@ EXPORTS = [
     "fsm_last_error", "fsm_get_stats", "fsm_get_kernel_stats", "fsm_db_from_spmf", "fsm_db_from_tokens",
     "fsm_db_free", "fsm_spade_mine", "fsm_patterns_free", "fsm_tsr_mine", "fsm_rules_free",
     "fsm_db_export", "fsm_db_image_free", "fsm_ingest", "fsm_token_db_free", "fsm_patterns_serialize",
-    "fsm_patterns_json", "fsm_rules_json", "fsm_buffer_free", "fsm_rules_query",
+    "fsm_patterns_json", "fsm_rules_json", "fsm_buffer_free", "fsm_rules_query", "fsm_patterns_filter",
 ]
 
 _lib = None
@@ -197,6 +198,8 @@ def load():
         L.fsm_buffer_free.restype = None
         L.fsm_rules_query.argtypes = [P(Rules), ctypes.c_int32, P(ctypes.c_int32), ctypes.c_int64,
                                       P(ctypes.c_int64), P(ctypes.c_int64)]
+    if hasattr(L, "fsm_patterns_filter"):
+        L.fsm_patterns_filter.argtypes = [vp, P(Patterns), ctypes.c_int32, P(P(Patterns)), P(ctypes.c_int64)]
     _lib = L
     return L
 

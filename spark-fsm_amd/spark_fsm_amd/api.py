@@ -56,12 +56,13 @@ class Rule:
         return "Rule(%r => %r, sup=%d, conf=%r)" % (self._x, self._y, self._sup, self._conf)
 
 
-def extract_rdd_patterns(dataset, support, dfs=True, stats=True, engine=None):
-    """SPADE.extractRDDPatterns (SPADE.scala:36-140) on the GPU engine."""
+def extract_rdd_patterns(dataset, support, dfs=True, stats=True, engine=None, keep="all"):
+    """SPADE.extractRDDPatterns (SPADE.scala:36-140) on the GPU engine.
+    keep="closed" / "maximal" (an extension): only the closed / maximal patterns."""
     eng = engine or default_engine()
     db = eng.db_from_spmf(list(dataset), MODE_SPADE)
     try:
-        pats, _meta = eng.spade(db, support, dfs)
+        pats, _meta = eng.spade(db, support, dfs, keep=keep)
     finally:
         db.free()
     if stats:  # algorithm.printStatistics() (SPADE.scala:136)

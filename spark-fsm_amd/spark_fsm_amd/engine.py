@@ -5,7 +5,9 @@ import weakref
 import numpy as np
 
 from . import _lib
-from ._lib import MODE_SPADE, MODE_TSR, check
+from ._lib import MODE_SPADE, MODE_TSR, KEEP_CLOSED, KEEP_MAXIMAL, check
+
+_KEEP = {"closed": KEEP_CLOSED, "maximal": KEEP_MAXIMAL}
 
 
 class _ResultOwner:
@@ -128,8 +130,53 @@ class Engine:
         return img
 
     # ------------------------------------------------------------ mining
-    def spade_csr(self, db, support, dfs=True, copy=False):
+    def _views(self, out, copy=False):
+        """A library-owned fsm_patterns -> the four CSR arrays (views sharing one owner, or copies)."""
+        owner = _ResultOwner(self._L.fsm_patterns_free, out)
+        p = out.contents
+        csr = (owner.view(p.support, p.n, np.int32), owner.view(p.pat_off, p.n + 1, np.int64),
+               owner.view(p.set_off, p.n_sets + 1, np.int64), owner.view(p.items, p.n_items, np.int32))
+        return tuple(a.copy() for a in csr) if copy else csr
+
+    def _filter(self, pats, keep, copy=False):
+        """fsm_patterns_filter on a _lib.Patterns (by reference) -> (csr, kept_idx)."""
+        code = _KEEP.get(keep)
+        if code is None:
+            raise ValueError("keep must be 'closed' or 'maximal' (got %r)" % (keep,))
+        out = ctypes.POINTER(_lib.Patterns)()
+        idx = np.empty(max(int(pats.n), 1), np.int64)
+        check(self._L.fsm_patterns_filter(self._ctx, ctypes.byref(pats), code, ctypes.byref(out),
+                                          idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))), self._ctx)
+        kept = idx[:out.contents.n].copy()
+        return self._views(out, copy), kept
+
+    def filter_patterns(self, csr, keep, copy=False):
+        """fsm_patterns_filter: the closed ("closed") or maximal ("maximal") patterns of a
+        COMPLETE frequent set, computed on the GPU.
+
+        csr is the (support, pat_off, set_off, items) tuple of spade_csr, or any numpy
+        arrays of that form.  Returns ((support, pat_off, set_off, items), kept_idx): the
+        kept patterns in input order, with spade_csr's view and ownership rules, and
+        their indexes in the input (int64, ascending)."""
+        sup, po, so, it = csr
+        sup = np.ascontiguousarray(sup, np.int32)
+        po = np.ascontiguousarray(po, np.int64)
+        so = np.ascontiguousarray(so, np.int64)
+        it = np.ascontiguousarray(it, np.int32)
+        if len(po) != len(sup) + 1 or len(so) < 1:
+            raise ValueError("pat_off must have n + 1 entries and set_off at least one")
+        P = ctypes.POINTER
+        pats = _lib.Patterns(len(sup), sup.ctypes.data_as(P(ctypes.c_int32)), po.ctypes.data_as(P(ctypes.c_int64)),
+                             so.ctypes.data_as(P(ctypes.c_int64)), it.ctypes.data_as(P(ctypes.c_int32)),
+                             len(so) - 1, len(it), 0, 0)
+        return self._filter(pats, keep, copy)
+
+    def spade_csr(self, db, support, dfs=True, copy=False, keep="all"):
         """fsm_spade_mine -> CSR numpy arrays (support, pat_off, set_off, items), meta.
+
+        keep="closed" / "maximal": the mined set goes through fsm_patterns_filter and
+        only the closed / maximal patterns are returned (meta["n"] counts them,
+        meta["n_mined"] the complete set).
 
         By default the arrays are read-only views of the library's result
         buffers (no copy of the hundreds of MB a dense mine returns).  The four
@@ -137,24 +184,26 @@ class Engine:
         is garbage-collected, so keeping any one of them (say only `support`)
         keeps every result buffer of the mine alive.  copy=True returns
         independent, writable copies and frees the library's buffers at once."""
+        if keep != "all" and keep not in _KEEP:
+            raise ValueError("keep must be 'all', 'closed' or 'maximal' (got %r)" % (keep,))
         out = ctypes.POINTER(_lib.Patterns)()
         check(self._L.fsm_spade_mine(self._ctx, db.handle, float(support), 1 if dfs else 0,
                                      ctypes.byref(out)), self._ctx)
-        owner = _ResultOwner(self._L.fsm_patterns_free, out)
         p = out.contents
-        n = p.n
-        sup = owner.view(p.support, n, np.int32)
-        po = owner.view(p.pat_off, n + 1, np.int64)
-        so = owner.view(p.set_off, p.n_sets + 1, np.int64)
-        it = owner.view(p.items, p.n_items, np.int32)
-        meta = {"total": p.total, "minsup": p.minsup, "n": n}
-        if copy:
-            sup, po, so, it = sup.copy(), po.copy(), so.copy(), it.copy()
-        return (sup, po, so, it), meta
+        meta = {"total": p.total, "minsup": p.minsup, "n": p.n}
+        if keep != "all":
+            try:
+                csr, _kept = self._filter(p, keep, copy)
+            finally:
+                self._L.fsm_patterns_free(out)  # the complete set is not returned
+            meta["n_mined"] = meta["n"]
+            meta["n"] = len(csr[0])
+            return csr, meta
+        return self._views(out, copy), meta
 
-    def spade(self, db, support, dfs=True):
+    def spade(self, db, support, dfs=True, keep="all"):
         """-> (patterns: list[(itemsets tuple-of-tuples, support)], meta dict)."""
-        (sup, po, so, it), meta = self.spade_csr(db, support, dfs)
+        (sup, po, so, it), meta = self.spade_csr(db, support, dfs, keep=keep)
         n = meta["n"]
         itl = it.tolist()
         sol = so.tolist()
@@ -188,7 +237,7 @@ class Engine:
         return MinedRules(self._L, out)
 
     def kernel_stats(self):
-        """[{name, launches, alg_bytes, survey_bytes, ms}] of the last mine call (device time, HIP
+        """[{name, launches, alg_bytes, survey_bytes, ms}] of the last mine or filter call (device time, HIP
         events; alg_bytes: the kernel's own layout, survey_bytes: SURVEY §8(d) units)."""
         n = ctypes.c_int32()
         check(self._L.fsm_get_kernel_stats(self._ctx, None, 0, ctypes.byref(n)), self._ctx)
