@@ -12,22 +12,38 @@
 // The entries of member m across all runs of its class ARE its id-list L(m).
 // Runs are laid out in parent-entry order (see k_emit).
 //
-// Kernels (one launch each per class batch):
-//   k_count        every (entry i, entry j) pair of a run evaluates the temporal /
-//                  equality join predicate of SURVEY A.2 and bumps the pair's
-//                  support counter: ALL n^2 candidate joins of a class in one
-//                  streaming pass over its entries (vs n^2 separate list merges).
-//   root F2        the root class (the F x 2F pair matrix, by far the largest):
-//                  one enumeration writes every entry's keys as a run, runs are
-//                  indexed by rank group and counted in LDS (k_root_* / k_group_*).
-//   k_freq_*       one wave per member row of the counter matrix: ballot the
-//                  frequent candidates (support >= minsup), give them child member
-//                  ids (wave prefix popcount), compact them for the host.
-//   k_emit         (entry, frequent child) pairs flattened across the lanes:
-//                  binary-search the partner entry in the (member-sorted) run,
-//                  write the child runs at scan offsets into the next slab.
-// The root class is the flattened DB restricted to frequent items (F1 = k_f1,
-// row filter = k_root_count / k_root_write).
+// Kernels, in the order a mine launches them:
+//   k_f1           F1: distinct-sequence support of every item.
+//   root           the root class is the flattened DB restricted to the frequent items.
+//                  DB-direct (default): no root slab, k_db_pos (row positions, once per
+//                  DB) and k_f2_plan_db (key capacities per rank group and row block)
+//                  read the DB rows.  Slab root: k_root_count + k_root_write_plan (or
+//                  k_root_write when the F2 geometry does not apply) write the slab.
+//   root F2        the F x 2F pair matrix, by far the largest: one enumeration writes
+//                  every entry's pair keys into its rank group's region (k_f2_tri:
+//                  unordered pairs, W = 1; k_f2_keys: ordered pairs), k_f2_count counts
+//                  a group's keys in LDS and writes only the frequent pairs out.
+//   class count    every (entry i, entry j) pair of a run evaluates the temporal /
+//                  equality join predicate of SURVEY A.2 and bumps the pair's support
+//                  counter: ALL n^2 candidate joins of a class in one streaming pass
+//                  over its entries (vs n^2 separate list merges).  k_count2 (windows
+//                  of whole runs; W <= 8) or k_count (a thread per entry) with global
+//                  atomics; keyed for join-dense batches (k_cnt_plan, k_cnt_keys,
+//                  k_f2_count<true>); sparse when the matrices exceed 4 GiB
+//                  (k_sparse_cap / _keys / _flag / _recs around a sort).
+//   k_freq_*       one wave per member row of the counter matrix: ballot the frequent
+//                  candidates (support >= minsup) and compact them as records; small
+//                  batches in one pass (k_freq_recs), large ones in row order
+//                  (k_freq_count, k_freq_write, with the kid table from k_kid_off).
+//   k_rk_*         a one-group batch's records ordered by (row, slot) on the device,
+//                  with the kid and child-class tables (hist, tables, scatter, row).
+//   emit           (entry, frequent child) pairs: find the partner entry in the
+//                  (member-sorted) run, write the child runs at a slab cursor.  k_emit2
+//                  (windows of whole runs in registers; W <= 8) hands its long runs to
+//                  k_emit1 (chunks, every W); the child class of a member slot comes
+//                  from k_child_flag + k_child_of or from the host.
+// The host side (below the kernels) drives them batch by batch: Miner::count_and_freq
+// lists the stages of one batch, SpadeKnobs the environment switches.
 #include <algorithm>
 #include <sys/mman.h>
 #include <cmath>
@@ -40,7 +56,9 @@
 #include <exception>
 #include <functional>
 #include <mutex>
+#include <optional>
 #include <thread>
+#include <type_traits>
 
 #include "comm.h"
 #include "dev_db.h"
@@ -2274,17 +2292,123 @@ __global__ __launch_bounds__(kBlock) void k_rk_row(const FreqRec* __restrict__ R
 
 // ------------------------------------------------------------- host side
 
-#define FSM_W_DISPATCH(W_, MACRO) \
-    switch (W_) {                 \
-        case 1: MACRO(1); break;  \
-        case 2: MACRO(2); break;  \
-        case 4: MACRO(4); break;  \
-        case 8: MACRO(8); break;  \
-        case 16: MACRO(16); break; \
-        case 32: MACRO(32); break; \
-        case 64: MACRO(64); break; \
-        default: MACRO(0); break;  \
+// Width dispatch: f(std::integral_constant<int, WW>{}) with the slab's mask words W as the
+// kernels' template argument WW.  with_width: every width (0 = the runtime width of any
+// other W).  with_window_width: the windowed kernels (k_count2, k_emit2) and the DB-direct
+// root, which exist for windowed_w(W) only.
+template <int WW> using WidthC = std::integral_constant<int, WW>;
+template <class F> void with_width(int W, F&& f) {
+    switch (W) {
+        case 1: f(WidthC<1>{}); break;
+        case 2: f(WidthC<2>{}); break;
+        case 4: f(WidthC<4>{}); break;
+        case 8: f(WidthC<8>{}); break;
+        case 16: f(WidthC<16>{}); break;
+        case 32: f(WidthC<32>{}); break;
+        case 64: f(WidthC<64>{}); break;
+        default: f(WidthC<0>{}); break;
     }
+}
+inline bool windowed_w(int W) { return W == 1 || W == 2 || W == 4 || W == 8; }
+template <class F> void with_window_width(int W, F&& f) {
+    switch (W) {
+        case 1: f(WidthC<1>{}); break;
+        case 2: f(WidthC<2>{}); break;
+        case 4: f(WidthC<4>{}); break;
+        default: f(WidthC<8>{}); break;
+    }
+}
+
+// The environment switches of a SPADE mine, read once when it starts (spade_mine) and held
+// const by its Miner: a mine sees one consistent set, and the next mine on the same context
+// sees the environment as it is then (tests, A/B runs and tuning flip them between mines).
+//   FSM_COUNT_PATH    atomic | keys | sparse force the class count path (else: by size)
+//   FSM_KEYED_MIN     entries from which a batch may take the keyed count (kKeyedMinEntries)
+//   FSM_ROOT_PATH     atomic: the root F2 by global atomics
+//   FSM_ROOT_DB       0: keep the root slab (k_root_count + k_root_write)
+//   FSM_F2_TRI        0: the ordered-pair root F2 (k_f2_keys) instead of k_f2_tri
+//   FSM_F2_BLOCKS     target row blocks of the root F2, [1, kF2MaxBlocks] (1024)
+//   FSM_COUNT_KERNEL  thread: k_count for every batch (default: k_count2 where W has it)
+//   FSM_COUNT_CHUNK   class entries per k_count block, [256, 2^20] (kChunk)
+//   FSM_KIDS          host: the kid table built on the host for every batch
+//   FSM_CHILD_OF      host | device: emit's child_of table (default: device from 2^17 member slots)
+//   FSM_EMIT_PATH     chunk: k_emit1 for every batch (default: k_emit2 where W has it)
+//   FSM_EMIT_CAP      lowers the LDS join records per wave of k_emit2 / k_emit1 (overflow paths)
+//   FSM_EMIT_GRID     grid cap of the emit kernels, [256, 2^22] (2^16)
+//   FSM_EMIT_DEFER    0: children built before the emit launch
+//   FSM_DEVORDER      0: a batch's records ordered on the host
+//   FSM_HOST_PAR_MIN  records from which the host tables are built by the thread pool, >= 1 (2^16)
+//   FSM_SPLIT_FRAC    sharded: a first-level class above this fraction of a rank's fair share
+//                     is split (0.5; <= 0: never)
+//   FSM_SPADE_CLAIMS  0: the static plan even with shared counters; 1: claims forced
+//   FSM_CLAIM_FIRST   a rank's first claim as a fraction of its fair share, [0.01, 64] (0.7)
+//   FSM_HOST_TRACE    1: host phase totals when the mine ends; 2: one line per batch
+//   FSM_DEBUG_DUMP    1: print every class row entry of small batches
+struct SpadeKnobs {
+    enum CountPath { kBySize, kAtomic, kKeys, kSparse };
+    enum ChildOf { kBySlots, kHost, kDevice };
+    CountPath count_path;
+    uint64_t keyed_min;
+    bool root_atomic, root_db, f2_tri;
+    uint32_t f2_blocks;
+    bool count_window;  // k_count2 where the width has it
+    uint32_t count_chunk;
+    bool kids_host;
+    ChildOf child_of;
+    bool emit_window;   // k_emit2 where the width has it
+    uint32_t emit2_cap, emit1_cap;
+    uint64_t emit_grid;
+    bool emit_defer, devorder;
+    uint64_t host_par_min;
+    double split_frac;  // (1e300: never split)
+    bool claims, claims_forced;
+    double claim_first;
+    int host_trace;
+    bool debug_dump;
+
+    static SpadeKnobs from_env() {
+        auto str = [](const char* name) { const char* v = std::getenv(name); return v ? v : ""; };
+        auto is = [&](const char* name, const char* val) { return !std::strcmp(str(name), val); };
+        auto lead = [&](const char* name, char c) { return str(name)[0] == c; };
+        auto num = [&](const char* name, uint64_t dflt) {
+            const char* v = std::getenv(name);
+            return v ? uint64_t(std::strtoull(v, nullptr, 10)) : dflt;
+        };
+        auto clamped = [&](const char* name, uint64_t lo, uint64_t hi, uint64_t dflt) {
+            return std::getenv(name) ? std::clamp<uint64_t>(num(name, 0), lo, hi) : dflt;
+        };
+        SpadeKnobs k;
+        k.count_path = is("FSM_COUNT_PATH", "atomic") ? kAtomic
+                       : is("FSM_COUNT_PATH", "keys") ? kKeys
+                       : is("FSM_COUNT_PATH", "sparse") ? kSparse : kBySize;
+        k.keyed_min = num("FSM_KEYED_MIN", kKeyedMinEntries);
+        k.root_atomic = is("FSM_ROOT_PATH", "atomic");
+        k.root_db = !lead("FSM_ROOT_DB", '0');
+        k.f2_tri = !lead("FSM_F2_TRI", '0');
+        k.f2_blocks = uint32_t(clamped("FSM_F2_BLOCKS", 1, kF2MaxBlocks, 1024));
+        k.count_window = !is("FSM_COUNT_KERNEL", "thread");
+        k.count_chunk = uint32_t(clamped("FSM_COUNT_CHUNK", 256, 1u << 20, kChunk));
+        k.kids_host = is("FSM_KIDS", "host");
+        k.child_of = is("FSM_CHILD_OF", "host") ? kHost : is("FSM_CHILD_OF", "device") ? kDevice : kBySlots;
+        k.emit_window = !is("FSM_EMIT_PATH", "chunk");
+        k.emit2_cap = uint32_t(std::min<uint64_t>(num("FSM_EMIT_CAP", kE2Cap), kE2Cap));
+        k.emit1_cap = uint32_t(std::min<uint64_t>(num("FSM_EMIT_CAP", kEmitCap), kEmitCap));
+        k.emit_grid = clamped("FSM_EMIT_GRID", 256, 1u << 22, 1u << 16);
+        k.emit_defer = !lead("FSM_EMIT_DEFER", '0');
+        k.devorder = !lead("FSM_DEVORDER", '0');
+        k.host_par_min = std::max<uint64_t>(1, num("FSM_HOST_PAR_MIN", uint64_t(1) << 16));
+        const char* sf = std::getenv("FSM_SPLIT_FRAC");
+        const double f = sf ? std::atof(sf) : 0.5;
+        k.split_frac = f > 0.0 ? f : 1e300;
+        k.claims = !lead("FSM_SPADE_CLAIMS", '0');
+        k.claims_forced = lead("FSM_SPADE_CLAIMS", '1');
+        const char* cf = std::getenv("FSM_CLAIM_FIRST");
+        k.claim_first = cf ? std::clamp(std::atof(cf), 0.01, 64.0) : 0.7;
+        k.host_trace = lead("FSM_HOST_TRACE", '1') ? 1 : lead("FSM_HOST_TRACE", '2') ? 2 : 0;
+        k.debug_dump = lead("FSM_DEBUG_DUMP", '1');
+        return k;
+    }
+};
 
 struct Slab {
     DevBuf cid, mem, lohi, pos, mask;
@@ -2426,123 +2550,139 @@ void order_recs(std::vector<FreqRec>& recs, uint32_t nrows, std::vector<uint32_t
     recs.swap(tmp);
 }
 
-struct Batch {
+// A batch's state comes in value-initialisable groups, so that Batch::recycle() resets a
+// group by assigning a fresh one: a field added to a group is reset with it.
+struct EventHolder {  // a HIP event created on first use, destroyed with its holder
+    hipEvent_t ev = nullptr;
+    EventHolder() = default;
+    EventHolder(EventHolder&& o) noexcept : ev(o.ev) { o.ev = nullptr; }
+    EventHolder& operator=(EventHolder&& o) noexcept {
+        std::swap(ev, o.ev);
+        return *this;
+    }
+    ~EventHolder() {
+        if (ev) (void)hipEventDestroy(ev);
+    }
+};
+// unsharded batches whose children fit one emit group: the children (pattern nodes and
+// the next batch's class tables) are built by emit() AFTER it has launched the emit
+// kernels, from these records (valid until the next count_and_freq), so that host work
+// overlaps the emit on the GPU instead of delaying its launch
+struct BatchDefer {
+    bool on = false;
+    const FreqRec* R = nullptr;
+    uint64_t n = 0, total = 0;
+    const RawVec<DRow>* rows = nullptr;
+    const uint32_t* child_of = nullptr;  // the child class of every member slot, on the device (with the kid table)
+};
+// the root batch: its F2 plan, the pair keys in flight and the DB-direct tables
+struct BatchRootF2 {
+    DevBuf root_rows;  // u64 [R+1] slab offset of every DB row's run
+    // F2 plan made by k_root_write_plan / k_f2_plan_db (region bases scanned, slot total read back)
+    bool planned = false;
+    DevBuf base;
+    uint64_t nslots = 0;
+    // the unordered-pair layout (k_f2_tri): [gtab: F | group start ranks: G + 1]
+    bool tri = false;
+    DevBuf tri_tab;
+    uint32_t tri_G = 0;
+    // its keys, launched by run_root_db right after the plan (the host's root bookkeeping
+    // then overlaps them): keys, region fills, the counters block, the clock ticket
+    bool launched = false;
+    DevBuf keys, fill, ctr_own;
+    char* ctr = nullptr;
+    size_t tk = 0;
+    // DB-direct root (no root slab): its kernels read the DB rows through rk2 (dense item ->
+    // member id, odd for an infrequent item)
+    DevBuf rk2;
+    DevBuf mem_db;  // u32 [DB entries]: each DB entry's member id rk2[item] (written by the F2 plan)
+};
+// sharded root with work stealing: children [0, nshared) are the heavy
+// classes every rank mines; the rest, largest first, are claimed in ranges from the
+// shared counter key (-1: no claims; groups fixed)
+struct BatchClaims {
+    int64_t key = -1;
+    size_t nshared = 0;
+    bool done = false;
+    int made = 0;
+    std::vector<uint64_t> pre;  // prefix volumes of the claimable children
+};
+// device buffers of a batch and the raw pointers into them
+struct BatchGpu {
     Slab slab;
-    RawVec<ClassMeta> cls;
-    // unsharded batches whose children fit one emit group: the children (pattern nodes and
-    // the next batch's class tables) are built by emit() AFTER it has launched the emit
-    // kernels, from these records (valid until the next count_and_freq), so that host work
-    // overlaps the emit on the GPU instead of delaying its launch
-    bool defer_children = false;
-    const FreqRec* defer_R = nullptr;
-    uint64_t defer_n = 0, defer_total = 0;
-    const RawVec<DRow>* defer_rows = nullptr;
-    const uint32_t* child_of_pre = nullptr;  // deferred, host child_of: uploaded with the kid table
-    // the root's unordered-pair F2 keys, launched by run_root_db right after its plan (the host's
-    // root bookkeeping then overlaps them): keys, region fills, the counters block
-    // the records ordered on the device (order_device): the kid and child-class tables are
-    // device-built; the ordered records reach pinned host memory at rec_ev
-    bool dev_order = false;
-    DevBuf ord_child_of;
-    hipEvent_t rec_ev = nullptr;
-    bool f2_launched = false;
-    DevBuf f2_keys, f2_fill, f2_ctr_own;
-    char* f2_ctr = nullptr;
-    size_t f2_tk = 0;
     DevBuf d_cls;
     DevBuf kid_tab;  // frequent children of every member (CSR over cbase + mi): offsets | slots | child ids
     const uint32_t* kid_off = nullptr;
     const uint32_t* kid_slot = nullptr;
     const uint32_t* kid_cid = nullptr;
     DevBuf child_pre;  // unsharded: u64 exclusive scan of "member slot has a child class" (emit's child_of)
-    uint64_t E = 0;                     // entries in the slab (runs of all classes, any order)
+    // the records ordered on the device (order_device): the kid and child-class tables are
+    // device-built; the ordered records reach pinned host memory at rec_ev
+    DevBuf ord_child_of;
+    EventHolder rec_ev;
+};
+struct BatchDims {
+    uint64_t E = 0;  // entries in the slab (runs of all classes, any order)
     uint64_t n_cnt = 0, cbase_total = 0;
+    size_t next_group = 0;
+    int64_t depth = 1;  // items per member pattern of this batch's classes
+    bool root = false;
+    uint64_t R = 0;          // root batch: the DB rows
+    bool db_direct = false;  // root batch: read from the DB rows (no root slab)
+    bool dev_order = false;  // the records were ordered on the device
+};
+
+struct Batch : BatchDims {
+    BatchDefer defer;
+    BatchRootF2 f2;
+    BatchClaims claim;
+    BatchGpu gpu;
+    // host tables: cleared with their capacity kept (the DFS reuses popped batches: no
+    // fresh pages per batch)
+    RawVec<ClassMeta> cls;
     RawVec<uint32_t> rank_item;  // member tables of cls (see ClassMeta)
     RawVec<int32_t> node_of;
     RawVec<ChildInfo> children;
     RawVec<uint32_t> child_rank_item;  // member tables of children
     RawVec<int32_t> child_node_of;
     std::vector<std::pair<size_t, size_t>> groups;
-    size_t next_group = 0;
-    int64_t depth = 1;  // items per member pattern of this batch's classes
-    bool root = false;
-    DevBuf root_rows;   // root batch: u64 [R+1] slab offset of every DB row's run
-    uint64_t R = 0;
-    // root batch: F2 plan made by k_root_write_plan (region bases scanned, slot total read back)
-    bool f2_planned = false;
-    DevBuf f2_base;
-    uint64_t f2_nslots = 0;
-    // the root F2 in the unordered-pair layout (k_f2_tri): [gtab: F | group start ranks: G + 1]
-    bool f2_tri = false;
-    DevBuf f2_tri_tab;
-    uint32_t f2_tri_G = 0;
-    // DB-direct root (no root slab): its kernels read the DB rows through rk2 (dense item ->
-    // member id, odd for an infrequent item)
-    bool db_direct = false;
-    DevBuf rk2;
-    DevBuf mem_db;  // u32 [DB entries]: each DB entry's member id rk2[item] (written by the F2 plan)
-    // sharded root with work stealing: children [0, nshared_children) are the
-    // heavy classes every rank mines; the rest, largest first, are claimed in ranges from the
-    // shared counter claim_key (-1: no claims; groups fixed)
-    int64_t claim_key = -1;
-    size_t nshared_children = 0;
-    bool claims_done = false;
-    int claims_made = 0;
-    std::vector<uint64_t> claim_pre;  // prefix volumes of the claimable children
 
-    // back to an empty batch: device buffers released, host vectors cleared with their
-    // capacity kept (the DFS reuses popped batches: no fresh pages per batch)
+    // back to an empty batch: device buffers released, host vectors cleared
     void recycle() {
-        slab = Slab{};
+        static_cast<BatchDims&>(*this) = {};
+        defer = {};
+        f2 = {};
+        claim = {};
+        gpu = {};
         cls.clear();
-        defer_children = false;
-        defer_R = nullptr;
-        defer_rows = nullptr;
-        child_of_pre = nullptr;
-        dev_order = false;
-        ord_child_of.release();
-        if (rec_ev) (void)hipEventDestroy(rec_ev);
-        rec_ev = nullptr;
-        f2_launched = false;
-        f2_keys.release();
-        f2_fill.release();
-        f2_ctr_own.release();
-        f2_ctr = nullptr;
-        defer_n = defer_total = 0;
-        d_cls.release();
-        kid_tab.release();
-        child_pre.release();
-        kid_off = kid_slot = kid_cid = nullptr;
-        E = n_cnt = cbase_total = 0;
         rank_item.clear();
         node_of.clear();
         children.clear();
         child_rank_item.clear();
         child_node_of.clear();
         groups.clear();
-        next_group = 0;
-        depth = 1;
-        root = false;
-        root_rows.release();
-        R = 0;
-        f2_planned = false;
-        f2_base.release();
-        f2_nslots = 0;
-        f2_tri = false;
-        f2_tri_tab.release();
-        f2_tri_G = 0;
-        db_direct = false;
-        rk2.release();
-        mem_db.release();
-        claim_key = -1;
-        nshared_children = 0;
-        claims_done = false;
-        claims_made = 0;
-        claim_pre.clear();
     }
 };
 
+// The ordered records of a batch row by row: f(q0, q1) for the records [q0, q1) of every
+// row that starts in [a, z) (a host-thread slice takes the rows that start in it, whole).
+template <class F> void for_row_groups(const FreqRec* R, uint64_t n, uint64_t a, uint64_t z, F&& f) {
+    uint64_t q = a;
+    while (a > 0 && q < z && R[q].row == R[q - 1].row) ++q;  // (a row that started before)
+    while (q < z) {
+        uint64_t q2 = q + 1;
+        while (q2 < n && R[q2].row == R[q].row) ++q2;
+        f(q, q2);
+        q = q2;
+    }
+}
+// a row's records [q0, q1) open a child class, unless its only record is an itemset extension
+inline bool opens_class(const FreqRec* R, uint64_t q0, uint64_t q1) {
+    return !(q1 - q0 == 1 && (R[q0].slot & 1u) == kItm);
+}
+
 struct Miner {
+    const SpadeKnobs knobs;
     fsm_ctx* ctx;
     SpadeDevDB* db;
     hipStream_t s;
@@ -2565,6 +2705,24 @@ struct Miner {
         zused += n;
         return p;
     }
+    // a zeroed device slot: from the block, or `own` (allocated and zeroed here) once it is used up
+    char* zeroed_slot(size_t bytes, DevBuf& own) {
+        if (void* p = zslot(bytes)) return static_cast<char*>(p);
+        own.alloc(bytes);
+        FSM_HIP(hipMemsetAsync(own.p, 0, bytes, s));
+        return own.as<char>();
+    }
+    // Extraction into a capped record buffer: run(cap, retry) launches it and returns the
+    // record count read back; a count above cap runs it once more at the exact size.
+    template <class F> uint32_t extract_capped(uint32_t cap, const char* overflow, F&& run) {
+        uint32_t n = run(cap, false);
+        if (n > cap) {  // rare: more records than the first buffer held
+            cap = n;
+            n = run(cap, true);
+            if (n > cap) throw Error(FSM_EDEVICE, overflow);
+        }
+        return n;
+    }
     unsigned long long* d_tests = nullptr;  // u64 (a zslot): (entry, partner) join tests of the class count kernels
     // sharded mining (nranks > 1): this rank counts the root rows of ranks
     // [slice_lo, slice_hi) and mines the first-level classes shard_plan gives it
@@ -2577,17 +2735,23 @@ struct Miner {
     RawVec<DRow> rows_s;
     std::vector<FreqRec> recs_s;
     RawVec<uint32_t> ktab_s, child_of_s;
-    std::vector<uint32_t> rec_off_s;  // row offsets of the records order_recs ordered last (kid offsets)
-    bool rec_off_ok = false;
+    std::vector<uint32_t> rec_off_s;  // row offsets of the records order_recs ordered last (Records::row_offsets)
     RawVec<uint64_t> gs_s;
     RawVec<uint32_t> r2_s;
 
     double wait_ms = 0;  // host time blocked on the stream (the rest of the lattice time is host work)
     // FSM_HOST_TRACE=1: host time of the bookkeeping phases, printed at the end of the mine
-    double hp[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // f2 sort, kids, children, groups, emit tables, slab alloc, count prep, count
-    // finer host split (FSM_HOST_TRACE): lap(i, t) adds the time since t to hq[i] and restarts t
-    double hq[16] = {};
-    void lap(int i, double& t) {
+    enum Phase { kF2Sort, kKids, kChildren, kGroups, kEmitTables, kSlabAlloc, kCountPrep, kCountExtract, kPhases };
+    static constexpr const char* kPhaseName[kPhases] = {"f2 sort", "kids", "children", "groups", "emit tables",
+                                                       "slab alloc", "count prep", "count+extract"};
+    double hp[kPhases] = {};
+    // finer host split (FSM_HOST_TRACE=1, printed by index): lap(i, t) adds the time since t
+    // to hq[i] and restarts t
+    enum Lap { kLapRowGroups, kLapChildSizes, kLapSpare, kLapChildAlloc, kLapChildFill, kLapCountMode, kLapPrepare,
+               kLapStats, kLapRows, kLapKidStage, kLapKidFill, kLapKidCopy, kLapDeferOk, kLapChildOf, kLapF2Recs,
+               kLapF2Order, kLaps };
+    double hq[kLaps] = {};
+    void lap(Lap i, double& t) {
         const double n = now_ms();
         hq[i] += n - t;
         t = n;
@@ -2711,34 +2875,22 @@ struct Miner {
                 });
             b.n_cnt = toff[size_t(nthr)];
             b.cbase_total = tcb[size_t(nthr)];
-            b.d_cls.alloc(std::max<size_t>(size_t(ncls) * sizeof(DClass), 4));
-            ctx->stage_copy(0, b.d_cls.p, size_t(ncls) * sizeof(DClass));
+            b.gpu.d_cls.alloc(std::max<size_t>(size_t(ncls) * sizeof(DClass), 4));
+            ctx->stage_copy(0, b.gpu.d_cls.p, size_t(ncls) * sizeof(DClass));
             return kl;
         }
         return false;
     }
 
-    // FSM_COUNT_PATH=atomic|keys: force the class count path (default: keyed for
-    // join-dense batches of >= kKeyedMinEntries entries; tests, profiling)
-    static int count_path() {
-        const char* v = std::getenv("FSM_COUNT_PATH");
-        if (!v) return 0;
-        return !std::strcmp(v, "keys") ? 2 : (!std::strcmp(v, "atomic") ? 1 : 0);
-    }
     // Keyed counting pays one group pass per kGroupCounters counters and a key pass
     // over the entries, atomics one memory-side atomic per join: keyed when the
     // batch's joins (estimated as sum cap^2 / runs, runs <= the prefix support)
     // reach both its counters and twice its entries.
-    // 0: global atomics (k_count), 1: keyed
+    // 0: global atomics (k_count), 1: keyed (knobs.count_path forces either)
     int count_mode(const Batch& b) const {
-        const int cp = count_path();
-        if (b.root || b.E == 0 || b.E >= kNone || cp == 1) return 0;
-        if (cp == 2) return 1;
-        static const uint64_t min_e = [] {  // FSM_KEYED_MIN overrides kKeyedMinEntries (tuning)
-            const char* v = std::getenv("FSM_KEYED_MIN");
-            return v ? uint64_t(std::strtoull(v, nullptr, 10)) : uint64_t(kKeyedMinEntries);
-        }();
-        if (b.E < min_e) return 0;
+        if (b.root || b.E == 0 || b.E >= kNone || knobs.count_path == SpadeKnobs::kAtomic) return 0;
+        if (knobs.count_path == SpadeKnobs::kKeys) return 1;
+        if (b.E < knobs.keyed_min) return 0;
         const int64_t ncls = int64_t(b.cls.size());
         const int64_t nthr = ncls >= (int64_t(1) << 15) ? host_threads() : 1;
         std::vector<double> te(size_t(nthr), 0), tn(size_t(nthr), 0);
@@ -2779,12 +2931,12 @@ struct Miner {
         const uint32_t nblk = uint32_t(std::min<uint64_t>(kF2MaxBlocks, std::max<uint64_t>(1, (b.E + FSM_CK_EPB - 1) / FSM_CK_EPB)));
         const uint32_t epb = (E + nblk - 1) / nblk;
         const uint64_t nd = uint64_t(G) * nblk;
-        const SlabPtrs sp = b.slab.ptrs();
+        const SlabPtrs sp = b.gpu.slab.ptrs();
         const uint32_t mlo = member_lo(b), mhi = member_hi(b);
         DevBuf cap(nd * 4), base((nd + 1) * 8), fill(nd * 4);
         size_t tk = clk->begin("k_cnt_plan");
         hipLaunchKernelGGL(k_cnt_plan, dim3(nblk), dim3(kF2Threads), size_t(G) * 4, s, E, epb, sp.cid,
-                           b.d_cls.as<DClass>(), sp.mem, sp.pos, mlo, mhi, G, nblk, cap.as<uint32_t>());
+                           b.gpu.d_cls.as<DClass>(), sp.mem, sp.pos, mlo, mhi, G, nblk, cap.as<uint32_t>());
         FSM_LAUNCHED("k_cnt_plan", s);
         clk->end(tk, int64_t(b.E * 12 + nd * 4));
         scan_exclusive(cap.as<uint32_t>(), base.as<uint64_t>(), nd, s);
@@ -2794,12 +2946,11 @@ struct Miner {
         if (nslots >= (uint64_t(1) << 32) - 4096) return false;  // region cursors are u32
         DevBuf keys((nslots + 1024) * 2);
         tk = clk->begin("k_cnt_keys");
-#define FSM_CK(WW)                                                                                                   \
-    hipLaunchKernelGGL(k_cnt_keys<WW>, dim3(nblk), dim3(kF2Threads), size_t(G) * 4, s, E, epb, sp.cid,                \
-                       b.d_cls.as<DClass>(), sp.mem, sp.lohi, sp.pos, sp.mask, mlo, mhi, G, nblk, base.as<uint64_t>(), \
-                       fill.as<uint32_t>(), keys.as<uint16_t>(), d_tests, uint32_t(W))
-        FSM_W_DISPATCH(W, FSM_CK)
-#undef FSM_CK
+        with_width(W, [&](auto w) {
+            hipLaunchKernelGGL(k_cnt_keys<decltype(w)::value>, dim3(nblk), dim3(kF2Threads), size_t(G) * 4, s, E, epb,
+                               sp.cid, b.gpu.d_cls.as<DClass>(), sp.mem, sp.lohi, sp.pos, sp.mask, mlo, mhi, G, nblk,
+                               base.as<uint64_t>(), fill.as<uint32_t>(), keys.as<uint16_t>(), d_tests, uint32_t(W));
+        });
         FSM_LAUNCHED("k_cnt_keys", s);
         clk->end(tk, int64_t(b.E * entry_bytes() + nd * 12), int64_t(b.E * survey_entry_bytes()));
         cnt.alloc(std::max<uint64_t>(G64 << kGroupShift, 1) * 4);
@@ -2819,12 +2970,10 @@ struct Miner {
     // sparse forces it: tests); sparse_count itself falls back (false) when the keys would
     // not be smaller than the matrices
     bool sparse_wanted(const Batch& b) const {
-        const char* v = std::getenv("FSM_COUNT_PATH");
-        if (v && !std::strcmp(v, "sparse")) return true;
-        return b.n_cnt * 4 >= (uint64_t(1) << 32);
+        return knobs.count_path == SpadeKnobs::kSparse || b.n_cnt * 4 >= (uint64_t(1) << 32);
     }
     bool sparse_count(Batch& b, std::vector<FreqRec>& recs, const RawVec<DRow>& rows) {
-        const SlabPtrs sp = b.slab.ptrs();
+        const SlabPtrs sp = b.gpu.slab.ptrs();
         const uint32_t E = uint32_t(b.E), mlo = member_lo(b), mhi = member_hi(b);
         const unsigned grid = unsigned(std::min<uint64_t>((b.E + kBlock - 1) / kBlock, 8192));
         DevBuf capd(8), cur(8), nruns(4);
@@ -2835,7 +2984,7 @@ struct Miner {
         FSM_HIP(hipMemcpyAsync(&pend[3], capd.p, 8, hipMemcpyDeviceToHost, s));
         sync();
         const uint64_t capk = pend[3];
-        const bool forced = [] { const char* v = std::getenv("FSM_COUNT_PATH"); return v && !std::strcmp(v, "sparse"); }();
+        const bool forced = knobs.count_path == SpadeKnobs::kSparse;
         // keys, their sorted copy, the unique keys and counts: about 28 B per key
         if (!forced && (capk * 28 >= b.n_cnt * 4 || capk * 28 > budget)) return false;
         recs.clear();
@@ -2843,12 +2992,11 @@ struct Miner {
         DevBuf keys(capk * 8), sorted(capk * 8);
         FSM_HIP(hipMemsetAsync(cur.p, 0, 8, s));
         const size_t tk = clk->begin("k_count");
-#define FSM_SK(WW)                                                                                                  \
-    hipLaunchKernelGGL(k_sparse_keys<WW>, dim3(grid), dim3(kBlock), 0, s, E, sp.cid, b.d_cls.as<DClass>(), sp.mem,   \
-                       sp.lohi, sp.pos, sp.mask, mlo, mhi, uint32_t(W), keys.as<unsigned long long>(),              \
-                       cur.as<unsigned long long>(), d_tests)
-        FSM_W_DISPATCH(W, FSM_SK)
-#undef FSM_SK
+        with_width(W, [&](auto w) {
+            hipLaunchKernelGGL(k_sparse_keys<decltype(w)::value>, dim3(grid), dim3(kBlock), 0, s, E, sp.cid,
+                               b.gpu.d_cls.as<DClass>(), sp.mem, sp.lohi, sp.pos, sp.mask, mlo, mhi, uint32_t(W),
+                               keys.as<unsigned long long>(), cur.as<unsigned long long>(), d_tests);
+        });
         FSM_LAUNCHED("k_sparse_keys", s);
         clk->end(tk, int64_t(b.E * entry_bytes()), int64_t(b.E * survey_entry_bytes()));
         FSM_HIP(hipMemcpyAsync(&pend[3], cur.p, 8, hipMemcpyDeviceToHost, s));
@@ -2887,31 +3035,33 @@ struct Miner {
         return true;
     }
 
-    void stats_for_class(const Batch& b, const ClassMeta& m) {
+    // the candidate joins of a class and the id-list bytes they would read as separate merges
+    struct ClassStats {
+        int64_t joins = 0, bytes = 0;
+        void operator+=(const ClassStats& o) {
+            joins += o.joins;
+            bytes += o.bytes;
+        }
+    };
+    static ClassStats class_stats(const ClassMeta& m) {
         const uint64_t S = m.nS, I = m.nI, sS = m.sS, sI = m.sI;
-        fsm_stats& st = ctx->stats;
-        const int64_t j = int64_t(S * S + I * S + (S ? S * (S - 1) / 2 : 0) + (I ? I * (I - 1) / 2 : 0));
-        st.joins += j;
-        if (b.root) st.joins_root += j;
         const uint64_t in = 2 * S * sS + S * sI + I * sS + (S ? (S - 1) * sS : 0) + (I ? (I - 1) * sI : 0);
-        st.bytes_join_equiv += int64_t(12 * in);
-        st.classes += 1;
+        return {int64_t(S * S + I * S + (S ? S * (S - 1) / 2 : 0) + (I ? I * (I - 1) / 2 : 0)), int64_t(12 * in)};
     }
 
     // FSM_DEBUG_DUMP=1: print every class row entry of small batches (debugging aid)
     void dump(Batch& b) {
-        static const bool on = [] { const char* v = std::getenv("FSM_DEBUG_DUMP"); return v && v[0] == '1'; }();
         const uint64_t n = b.E;
-        if (!on || n > 4096 || b.db_direct) return;
+        if (!knobs.debug_dump || n > 4096 || b.db_direct) return;
         std::vector<uint32_t> cid(n), mem(n), lohi(n), pos(n);
         std::vector<uint64_t> mk(n * uint64_t(W));
-        FSM_HIP(hipMemcpyAsync(cid.data(), b.slab.cid.p, n * 4, hipMemcpyDeviceToHost, s));
-        FSM_HIP(hipMemcpyAsync(mem.data(), b.slab.mem.p, n * 4, hipMemcpyDeviceToHost, s));
-        if (b.slab.lohi.p) FSM_HIP(hipMemcpyAsync(lohi.data(), b.slab.lohi.p, n * 4, hipMemcpyDeviceToHost, s));
-        FSM_HIP(hipMemcpyAsync(pos.data(), b.slab.pos.p, n * 4, hipMemcpyDeviceToHost, s));
-        FSM_HIP(hipMemcpyAsync(mk.data(), b.slab.mask.p, n * 8 * W, hipMemcpyDeviceToHost, s));
+        FSM_HIP(hipMemcpyAsync(cid.data(), b.gpu.slab.cid.p, n * 4, hipMemcpyDeviceToHost, s));
+        FSM_HIP(hipMemcpyAsync(mem.data(), b.gpu.slab.mem.p, n * 4, hipMemcpyDeviceToHost, s));
+        if (b.gpu.slab.lohi.p) FSM_HIP(hipMemcpyAsync(lohi.data(), b.gpu.slab.lohi.p, n * 4, hipMemcpyDeviceToHost, s));
+        FSM_HIP(hipMemcpyAsync(pos.data(), b.gpu.slab.pos.p, n * 4, hipMemcpyDeviceToHost, s));
+        FSM_HIP(hipMemcpyAsync(mk.data(), b.gpu.slab.mask.p, n * 8 * W, hipMemcpyDeviceToHost, s));
         sync();
-        if (!b.slab.lohi.p)  // (W = 1: derived from the mask)
+        if (!b.gpu.slab.lohi.p)  // (W = 1: derived from the mask)
             for (uint64_t e = 0; e < n; ++e)
                 lohi[e] = mk[e] ? uint32_t(__builtin_ctzll(mk[e])) | ((63u - uint32_t(__builtin_clzll(mk[e]))) << 16) : 0u;
         std::fprintf(stderr, "[dump] depth=%lld classes=%zu\n", (long long)b.depth, b.cls.size());
@@ -2927,85 +3077,21 @@ struct Miner {
     uint32_t member_lo(const Batch& b) const { return comm && b.root ? 2 * slice_lo : 0u; }
     uint32_t member_hi(const Batch& b) const { return comm && b.root ? 2 * slice_hi : kNone; }
 
-    // FSM_ROOT_PATH=atomic forces the global-atomic root F2 path (tests, profiling).
-    static bool root_atomic() {
-        const char* v = std::getenv("FSM_ROOT_PATH");
-        return v && !std::strcmp(v, "atomic");
-    }
-    // grid cap of k_emit (FSM_EMIT_GRID overrides, for tuning)
-    static uint64_t emit_grid_cap() {
-        const char* v = std::getenv("FSM_EMIT_GRID");
-        return v ? std::clamp<uint64_t>(std::strtoull(v, nullptr, 10), 256, 1u << 22) : (1u << 16);
-    }
-    // sharded mining: a first-level class whose estimated volume exceeds this fraction of a
-    // rank's fair share is split (FSM_SPLIT_FRAC overrides; 0 or less disables splitting)
-    static double split_frac() {
-        const char* v = std::getenv("FSM_SPLIT_FRAC");
-        const double f = v ? std::atof(v) : 0.5;
-        return f > 0.0 ? f : 1e300;
-    }
-    // FSM_COUNT_KERNEL=thread forces the thread-per-entry k_count (tests, A/B runs; default: k_count2 at W = 1)
-    static bool count_window() {
-        const char* v = std::getenv("FSM_COUNT_KERNEL");
-        return !(v && !std::strcmp(v, "thread"));
-    }
-    // FSM_KIDS=host builds the kid table on the host for every batch (tests, A/B; default:
-    // large unsharded batches get it from k_freq_write + k_kid_off on the device)
-    static bool kids_host() {
-        const char* v = std::getenv("FSM_KIDS");
-        return v && !std::strcmp(v, "host");
-    }
-    // FSM_EMIT_PATH=chunk forces k_emit1 for every batch (tests, A/B runs; default: k_emit2 at W = 1)
-    static bool emit_window() {
-        const char* v = std::getenv("FSM_EMIT_PATH");
-        return !(v && !std::strcmp(v, "chunk"));
-    }
-    // emit's child_of table: built on the device for unsharded batches of at least 2^17
-    // member slots (below that the launches cost more than the host fill + copy);
-    // FSM_CHILD_OF=host / device forces either (tests, A/B)
-    static bool child_of_device(uint64_t slots) {
-        const char* v = std::getenv("FSM_CHILD_OF");
-        if (v && !std::strcmp(v, "host")) return false;
-        if (v && !std::strcmp(v, "device")) return true;
-        return slots >= (uint64_t(1) << 17);
-    }
-    // LDS join records per wave of k_emit2 (FSM_EMIT_CAP lowers it too: tests of the overflow path)
-    static uint32_t emit2_cap() {
-        const char* v = std::getenv("FSM_EMIT_CAP");
-        return v ? uint32_t(std::min<uint64_t>(std::strtoull(v, nullptr, 10), kE2Cap)) : kE2Cap;
-    }
-    // LDS join records per wave of k_emit1 (FSM_EMIT_CAP lowers it: tests of the overflow path)
-    static uint32_t emit_cap() {
-        const char* v = std::getenv("FSM_EMIT_CAP");
-        return v ? uint32_t(std::min<uint64_t>(std::strtoull(v, nullptr, 10), kEmitCap)) : kEmitCap;
-    }
-    // class entries per block of k_count (FSM_COUNT_CHUNK overrides, for tuning)
-    static uint32_t count_chunk() {
-        const char* v = std::getenv("FSM_COUNT_CHUNK");
-        return v ? uint32_t(std::clamp<uint64_t>(std::strtoull(v, nullptr, 10), 256, 1u << 20)) : kChunk;
-    }
     // key alignment of the root F2 regions: 8 keys, so k_f2_count reads them in 16-byte words (64 or 256
     // measured no different in round 4)
     static constexpr uint32_t kF2Align = 8;
-    // records from which the kid table and the children of a batch are built on the host
-    // thread pool (below: one thread); FSM_HOST_PAR_MIN overrides (tuning)
-    static uint64_t par_min() {
-        static const uint64_t v = [] {
-            const char* e = std::getenv("FSM_HOST_PAR_MIN");
-            return e ? std::max<uint64_t>(1, std::strtoull(e, nullptr, 10)) : uint64_t(1) << 16;
-        }();
-        return v;
-    }
     // whether the DB-direct root's F2 takes the unordered-pair layout (run_root_db decides it the
     // same way, unless the rank's own slice is empty)
     bool tri_expected(uint32_t F) const {
-        return W == 1 && f2_tri_env() && F > 0 && tri_len(F, 0) <= kGroupCounters &&
-               root_db_env() && !root_atomic();
+        return W == 1 && knobs.f2_tri && F > 0 && tri_len(F, 0) <= kGroupCounters && knobs.root_db &&
+               !knobs.root_atomic;
     }
-    // the root F2 in the unordered-pair layout (k_f2_tri; FSM_F2_TRI=0: the ordered layout)
-    static bool f2_tri_env() {
-        const char* v = std::getenv("FSM_F2_TRI");
-        return !(v && v[0] == '0');
+    // emit's child_of table: built on the device for unsharded batches of at least 2^17
+    // member slots (below that the launches cost more than the host fill + copy), unless
+    // FSM_CHILD_OF forces either
+    bool child_of_device(uint64_t slots) const {
+        if (knobs.child_of != SpadeKnobs::kBySlots) return knobs.child_of == SpadeKnobs::kDevice;
+        return slots >= (uint64_t(1) << 17);
     }
     // groups of the unordered-pair layout over the rows [rlo, rhi) of F ranks: gtab[i] = group <<
     // kGroupShift | first counter of row i; gr = the groups' first rows (G + 1).  0 groups: a
@@ -3030,11 +3116,6 @@ struct Miner {
         tab.insert(tab.end(), gr.begin(), gr.end());
         return G;
     }
-    // row blocks of the root F2 (FSM_F2_BLOCKS overrides the target count, for tuning)
-    static uint32_t f2_blocks() {
-        const char* v = std::getenv("FSM_F2_BLOCKS");
-        return v ? uint32_t(std::clamp<uint64_t>(std::strtoull(v, nullptr, 10), 1, kF2MaxBlocks)) : 1024u;
-    }
 
     // Root F2 by rank groups (plan / k_f2_keys / k_f2_count): the
     // frequent (rank, slot) pairs of this rank's slice, sorted by (row, slot),
@@ -3051,7 +3132,7 @@ struct Miner {
     F2Geo f2_geometry(const Batch& b, uint32_t D, uint64_t nent, uint64_t Rrows) const {
         F2Geo g;
         const uint32_t F = D / 2;
-        if (nent == 0 || D > kGroupCounters || Rrows == 0 || F >= (1u << 15) || root_atomic()) return g;
+        if (nent == 0 || D > kGroupCounters || Rrows == 0 || F >= (1u << 15) || knobs.root_atomic) return g;
         g.D = D;
         g.F = F;
         g.per = kGroupCounters / D;
@@ -3061,7 +3142,7 @@ struct Miner {
         g.mlo = member_lo(b);
         g.mhi = member_hi(b);
         g.R = uint32_t(Rrows);
-        const uint32_t nb_want = std::min<uint32_t>(f2_blocks(), kF2MaxBlocks);
+        const uint32_t nb_want = std::min<uint32_t>(knobs.f2_blocks, kF2MaxBlocks);
         g.rpb = std::min<uint32_t>(kF2MaxRows, std::max<uint32_t>(16u, (g.R + nb_want - 1) / nb_want));
         if (uint64_t(g.rpb) * kF2MaxBlocks < g.R) return g;  // more rows than the LDS-indexed blocks cover
         g.nblk = (g.R + g.rpb - 1) / g.rpb;
@@ -3072,219 +3153,172 @@ struct Miner {
 
     bool root_f2(Batch& b, std::vector<FreqRec>& recs) {
         const ClassMeta& m = b.cls[0];
-        if (b.root_rows.p == nullptr && !b.db_direct) return false;
+        if (b.f2.root_rows.p == nullptr && !b.db_direct) return false;
         const F2Geo geo = f2_geometry(b, m.D, m.cap, b.R);
         if (!geo.ok) return false;
         const uint32_t D = geo.D, F = geo.F, per = geo.per, G = geo.G, pm = geo.pm, mlo = geo.mlo, mhi = geo.mhi;
         const uint32_t rlo = comm ? slice_lo : 0u, rhi = comm ? std::min(slice_hi, F) : F;
         const uint32_t R = geo.R, rpb = geo.rpb, nblk = geo.nblk;
-        if (b.f2_tri) return root_f2_tri(b, recs, geo, rlo, rhi);
+        if (b.f2.tri) return root_f2_tri(b, recs, geo, rlo, rhi);
         const uint64_t nd = geo.nd;
-        const SlabPtrs sp = b.slab.ptrs();
+        const SlabPtrs sp = b.gpu.slab.ptrs();
         const int64_t E0 = int64_t(m.cap);
-        if (!b.f2_planned) return false;  // the plan is made while the root rows are written
-        DevBuf base = std::move(b.f2_base), fill(nd * 4);
-        const uint64_t nslots = b.f2_nslots;
-
+        if (!b.f2.planned) return false;  // the plan is made while the root rows are written
+        DevBuf base = std::move(b.f2.base), fill(nd * 4);
+        const uint64_t nslots = b.f2.nslots;
         if (nslots >= (uint64_t(1) << 32) - 4096) return false;  // region cursors are u32
         // the one enumeration (keys padded: k_f2_count reads whole 16-byte words past a region's end)
-        DevBuf keys((nslots + 1024) * 2), ctr_own;
-        // u64 key count | u32 frequent-record count, read back together
-        char* ctr = static_cast<char*>(zslot(16));
-        if (!ctr) {
-            ctr_own.alloc(16);
-            FSM_HIP(hipMemsetAsync(ctr_own.p, 0, 16, s));
-            ctr = ctr_own.as<char>();
-        }
+        DevBuf keys((nslots + 1024) * 2), ctr_own, d_recs;
+        char* ctr = zeroed_slot(16, ctr_own);  // u64 key count | u32 frequent-record count
         unsigned long long* nk = reinterpret_cast<unsigned long long*>(ctr);
         uint32_t* d_nrec = reinterpret_cast<uint32_t*>(ctr + 8);
         const size_t kshm = size_t(kF2Waves) * 64 * (sizeof(F2Ent) + sizeof(F2Act)) + size_t(kF2RowWords) * 4 + size_t(G) * 4;
+        const size_t tk_keys = clk->begin("k_f2_keys");
+        if (b.db_direct) {
+            with_window_width(W, [&](auto w) {
+                hipLaunchKernelGGL((k_f2_keys<decltype(w)::value, true>), dim3(nblk), dim3(kF2Threads), kshm, s,
+                                   (const uint64_t*)nullptr, db->row_off.as<uint32_t>(),
+                                   RootRef{db->item.as<uint32_t>(), b.f2.rk2.as<uint32_t>()}, R, rpb,
+                                   b.f2.mem_db.as<uint32_t>(), (const uint32_t*)nullptr, db->mask.as<uint64_t>(), D, per, pm,
+                                   G, nblk, mlo, mhi, base.as<uint64_t>(), fill.as<uint32_t>(), keys.as<uint16_t>(), nk,
+                                   uint32_t(W));
+            });
+        } else {
+            with_width(W, [&](auto w) {
+                hipLaunchKernelGGL((k_f2_keys<decltype(w)::value, false>), dim3(nblk), dim3(kF2Threads), kshm, s,
+                                   b.f2.root_rows.as<uint64_t>(), (const uint32_t*)nullptr, RootRef{nullptr, nullptr}, R,
+                                   rpb, sp.mem, sp.lohi, sp.mask, D, per, pm, G, nblk, mlo, mhi, base.as<uint64_t>(),
+                                   fill.as<uint32_t>(), keys.as<uint16_t>(), nk, uint32_t(W));
+            });
+        }
+        FSM_LAUNCHED("k_f2_keys", s);
+        // reads the slab (mem, lohi, mask) and the region bases, writes the fills;
+        // + 2 B per key actually written, added once the count is back
+        // DB-direct: the DB rows (item + mask per entry) instead of the slab's (mem, lohi, mask)
+        const int64_t rowb = b.db_direct ? db->E * int64_t(4 + 8 * W) : E0 * int64_t(8 + 8 * W);
+        clk->end(tk_keys, rowb + int64_t(nd) * 12, E0 * 8);
         // count + frequent pairs of this rank's slice
-        const uint32_t g0 = rlo / per, g1 = rhi == 0 ? 0u : (rhi - 1) / per + 1;
-        uint32_t cap_recs = uint32_t(std::min<uint64_t>(uint64_t(rhi - rlo) * D, uint64_t(1) << 20));
-        DevBuf d_recs;
-        unsigned long long nkeys = 0;
-        size_t tk_cnt = 0, tk_keys = 0;
         // (one pass over every group of the slice: passes over group ranges, which keep a pass's
         // keys on-die, measured slower in round 4: each pass enumerates the rows again)
-        for (int attempt = 0;; ++attempt) {
-            d_recs.alloc(std::max<uint32_t>(cap_recs, 1) * sizeof(FreqRec));
-            if (attempt > 0) FSM_HIP(hipMemsetAsync(d_nrec, 0, 4, s));
-            {
-                const uint32_t pg0 = g0, pg1 = g1, prlo = rlo, prhi = rhi;
-                if (attempt == 0) {  // a retry (record overflow) counts from the keys already written
-                    const uint32_t pmlo = mlo, pmhi = mhi;
-                    tk_keys = clk->begin("k_f2_keys");
-#define FSM_F2K(WW)                                                                                                   \
-    hipLaunchKernelGGL((k_f2_keys<WW, false>), dim3(nblk), dim3(kF2Threads), kshm, s, b.root_rows.as<uint64_t>(),      \
-                       (const uint32_t*)nullptr, RootRef{nullptr, nullptr}, R, rpb, sp.mem, sp.lohi, sp.mask, D, per,  \
-                       pm, G, nblk, pmlo, pmhi, base.as<uint64_t>(), fill.as<uint32_t>(), keys.as<uint16_t>(),        \
-                       nk, uint32_t(W))
-#define FSM_F2KD(WW)                                                                                                  \
-    hipLaunchKernelGGL((k_f2_keys<WW, true>), dim3(nblk), dim3(kF2Threads), kshm, s, (const uint64_t*)nullptr,         \
-                       db->row_off.as<uint32_t>(), RootRef{db->item.as<uint32_t>(), b.rk2.as<uint32_t>()}, R, rpb,     \
-                       b.mem_db.as<uint32_t>(), (const uint32_t*)nullptr, db->mask.as<uint64_t>(), D, per, pm, G,      \
-                       nblk, pmlo, pmhi, base.as<uint64_t>(), fill.as<uint32_t>(), keys.as<uint16_t>(),               \
-                       nk, uint32_t(WW))
-                    if (b.db_direct) {
-                        switch (W) {
-                            case 1: FSM_F2KD(1); break;
-                            case 2: FSM_F2KD(2); break;
-                            case 4: FSM_F2KD(4); break;
-                            default: FSM_F2KD(8); break;
-                        }
-                    } else {
-                        FSM_W_DISPATCH(W, FSM_F2K)
-                    }
-#undef FSM_F2K
-#undef FSM_F2KD
-                    FSM_LAUNCHED("k_f2_keys", s);
-                    // reads the slab (mem, lohi, mask) and the region bases, writes the fills;
-                    // + 2 B per key actually written, added once the count is back
-                    // DB-direct: the DB rows (item + mask per entry) instead of the slab's (mem, lohi, mask)
-                    const int64_t rowb = b.db_direct ? db->E * int64_t(4 + 8 * W) : E0 * int64_t(8 + 8 * W);
-                    clk->end(tk_keys, rowb + int64_t(nd) * 12, E0 * 8);
-                }
+        const uint32_t g0 = rlo / per, g1 = rhi == 0 ? 0u : (rhi - 1) / per + 1;
+        size_t tk_cnt = 0;
+        const uint32_t nrec = extract_capped(
+            uint32_t(std::min<uint64_t>(uint64_t(rhi - rlo) * D, uint64_t(1) << 20)),
+            "SPADE root F2: frequent pair buffer overflow", [&](uint32_t cap, bool retry) {
+                d_recs.alloc(std::max<uint32_t>(cap, 1) * sizeof(FreqRec));
+                if (retry) FSM_HIP(hipMemsetAsync(d_nrec, 0, 4, s));  // (counts from the keys already written)
                 tk_cnt = clk->begin("k_f2_count");
-                if (pg1 > pg0)
-                    hipLaunchKernelGGL(k_f2_count<false>, dim3(pg1 - pg0), dim3(kF2Threads), 0, s, base.as<uint64_t>(),
-                                       fill.as<uint32_t>(), nblk, keys.as<uint16_t>(), D, per, pg0, prlo, prhi, minsup,
-                                       d_recs.as<FreqRec>(), cap_recs, d_nrec, (uint32_t*)nullptr, 1u);
+                if (g1 > g0)
+                    hipLaunchKernelGGL(k_f2_count<false>, dim3(g1 - g0), dim3(kF2Threads), 0, s, base.as<uint64_t>(),
+                                       fill.as<uint32_t>(), nblk, keys.as<uint16_t>(), D, per, g0, rlo, rhi, minsup,
+                                       d_recs.as<FreqRec>(), cap, d_nrec, (uint32_t*)nullptr, 1u);
                 FSM_LAUNCHED("k_f2_count", s);
-                clk->end(tk_cnt, int64_t(pg1 - pg0) * nblk * 12);
-            }
-            pend[2] = pend[3] = 0;
-            FSM_HIP(hipMemcpyAsync(&pend[2], ctr, 16, hipMemcpyDeviceToHost, s));  // (one copy: both counts)
-            sync();
-            nkeys = pend[2];
-            const uint32_t nrec = uint32_t(pend[3] & 0xFFFFFFFFu);
-            if (nrec <= cap_recs || attempt > 0) {
-                if (nrec > cap_recs) throw Error(FSM_EDEVICE, "SPADE root F2: frequent pair buffer overflow");
-                recs.resize(nrec);
-                if (nrec)
-                    FSM_HIP(hipMemcpyAsync(recs.data(), d_recs.p, size_t(nrec) * sizeof(FreqRec), hipMemcpyDeviceToHost,
-                                           s));
-                sync();
-                break;
-            }
-            cap_recs = nrec;  // rare: more frequent pairs than the first buffer held; count again
-        }
-        clk->add_bytes(tk_keys, int64_t(nkeys) * 2);
-        clk->add_bytes(tk_cnt, int64_t(nkeys) * 2 + int64_t(recs.size() * sizeof(FreqRec)));
-        ctx->stats.root_keys += int64_t(nkeys);
-        // (row, slot) order and child member ids: rank among the row's slots with a frequent
-        // temporal or equality candidate, << 1 | type (as k_freq_write assigns them)
-        const double th0 = now_ms();
-        order_recs(recs, F, &rec_off_s);
-        rec_off_ok = true;
-        hp[0] += now_ms() - th0;
+                clk->end(tk_cnt, int64_t(g1 - g0) * nblk * 12);
+                return read_f2_counts(ctr);
+            });
+        recs.resize(nrec);
+        if (nrec) FSM_HIP(hipMemcpyAsync(recs.data(), d_recs.p, size_t(nrec) * sizeof(FreqRec), hipMemcpyDeviceToHost, s));
+        sync();
+        root_f2_account(tk_keys, tk_cnt, nrec);
+        order_root_recs(recs, F);
         return true;
     }
+    // both counts of a root F2 counter block in one copy: the frequent records; the keys stay in pend[2]
+    uint32_t read_f2_counts(const char* ctr) {
+        pend[2] = pend[3] = 0;
+        FSM_HIP(hipMemcpyAsync(&pend[2], ctr, 16, hipMemcpyDeviceToHost, s));
+        sync();
+        return uint32_t(pend[3] & 0xFFFFFFFFu);
+    }
+    // the keys actually written (pend[2]) into the two kernels' byte counts and the stats
+    void root_f2_account(size_t tk_keys, size_t tk_cnt, uint32_t nrec) {
+        const int64_t nkeys = int64_t(pend[2]);
+        clk->add_bytes(tk_keys, nkeys * 2);
+        clk->add_bytes(tk_cnt, nkeys * 2 + int64_t(nrec) * int64_t(sizeof(FreqRec)));
+        ctx->stats.root_keys += nkeys;
+    }
+    // (row, slot) order and child member ids: rank among the row's slots with a frequent
+    // temporal or equality candidate, << 1 | type (as k_freq_write assigns them)
+    void order_root_recs(std::vector<FreqRec>& recs, uint32_t F) {
+        double t = now_ms();
+        order_recs(recs, F, &rec_off_s);
+        hp[kF2Sort] += now_ms() - t;
+        lap(kLapF2Order, t);
+    }
+    // the k_f2_tri launch of the root (once; false: the slot count exceeds the u32 cursors)
+    bool launch_f2_tri(Batch& b, const F2Geo& geo) {
+        if (b.f2.launched) return true;
+        const uint32_t G = b.f2.tri_G, R = geo.R, rpb = geo.rpb, nblk = geo.nblk;
+        const uint64_t nd = uint64_t(G) * nblk;
+        const uint64_t nslots = b.f2.nslots;
+        if (nslots >= (uint64_t(1) << 32) - 4096) return false;
+        b.f2.fill.alloc(nd * 4);
+        b.f2.keys.alloc((nslots + 1024) * 2);
+        // u64 key count | u32 frequent-record count, read back together
+        b.f2.ctr = zeroed_slot(16, b.f2.ctr_own);
+        const uint32_t* gtab = b.f2.tri_tab.as<uint32_t>();
+        const size_t kshm = size_t(kF2Waves) * 64 * 16 + size_t(kF2RowWords) * 4 + size_t(G) * 4;
+        b.f2.tk = clk->begin("k_f2_keys");
+        hipLaunchKernelGGL(k_f2_tri, dim3(nblk), dim3(kF2Threads), kshm, s, db->row_off.as<uint32_t>(),
+                           b.f2.mem_db.as<uint32_t>(), db->mask.as<uint64_t>(), R, rpb, gtab, G, nblk, geo.mlo, geo.mhi,
+                           b.f2.base.as<uint64_t>(), b.f2.fill.as<uint32_t>(), b.f2.keys.as<uint16_t>(),
+                           reinterpret_cast<unsigned long long*>(b.f2.ctr));
+        FSM_LAUNCHED("k_f2_tri", s);
+        clk->end(b.f2.tk, db->E * 12 + int64_t(nd) * 12, int64_t(b.cls[0].cap) * 8);
+        b.f2.launched = true;
+        return true;
+    }
+
     // The root F2 in the unordered-pair layout (k_f2_plan_db with the group table, k_f2_tri,
     // k_f2_count<false, true>): the frequent ordered pairs of the rows [rlo, rhi), as records
     // in (row, slot) order.  A pair (i, j) counts where the lower rank i is owned, so a rank's
     // records also hold rows j above its slice (the sharded gather orders them again).
-    // the k_f2_tri launch of the root (once; false: the slot count exceeds the u32 cursors)
-    bool launch_f2_tri(Batch& b, const F2Geo& geo) {
-        if (b.f2_launched) return true;
-        const uint32_t G = b.f2_tri_G, R = geo.R, rpb = geo.rpb, nblk = geo.nblk;
-        const uint64_t nd = uint64_t(G) * nblk;
-        const uint64_t nslots = b.f2_nslots;
-        if (nslots >= (uint64_t(1) << 32) - 4096) return false;
-        b.f2_fill.alloc(nd * 4);
-        b.f2_keys.alloc((nslots + 1024) * 2);
-        // u64 key count | u32 frequent-record count, read back together
-        b.f2_ctr = static_cast<char*>(zslot(16));
-        if (!b.f2_ctr) {
-            b.f2_ctr_own.alloc(16);
-            FSM_HIP(hipMemsetAsync(b.f2_ctr_own.p, 0, 16, s));
-            b.f2_ctr = b.f2_ctr_own.as<char>();
-        }
-        const uint32_t* gtab = b.f2_tri_tab.as<uint32_t>();
-        const size_t kshm = size_t(kF2Waves) * 64 * 16 + size_t(kF2RowWords) * 4 + size_t(G) * 4;
-        b.f2_tk = clk->begin("k_f2_keys");
-        hipLaunchKernelGGL(k_f2_tri, dim3(nblk), dim3(kF2Threads), kshm, s, db->row_off.as<uint32_t>(),
-                           b.mem_db.as<uint32_t>(), db->mask.as<uint64_t>(), R, rpb, gtab, G, nblk, geo.mlo, geo.mhi,
-                           b.f2_base.as<uint64_t>(), b.f2_fill.as<uint32_t>(), b.f2_keys.as<uint16_t>(),
-                           reinterpret_cast<unsigned long long*>(b.f2_ctr));
-        FSM_LAUNCHED("k_f2_tri", s);
-        clk->end(b.f2_tk, db->E * 12 + int64_t(nd) * 12, int64_t(b.cls[0].cap) * 8);
-        b.f2_launched = true;
-        return true;
-    }
-
     bool root_f2_tri(Batch& b, std::vector<FreqRec>& recs, const F2Geo& geo, uint32_t rlo, uint32_t rhi) {
-        const uint32_t F = geo.F, G = b.f2_tri_G, nblk = geo.nblk;
+        const uint32_t F = geo.F, G = b.f2.tri_G, nblk = geo.nblk;
         if (!launch_f2_tri(b, geo)) return false;
-        DevBuf base = std::move(b.f2_base), fill = std::move(b.f2_fill), keys = std::move(b.f2_keys),
-               ctr_own = std::move(b.f2_ctr_own);
-        char* ctr = b.f2_ctr;
-        const size_t tk_keys = b.f2_tk;
+        DevBuf base = std::move(b.f2.base), fill = std::move(b.f2.fill), keys = std::move(b.f2.keys),
+               ctr_own = std::move(b.f2.ctr_own);
+        char* ctr = b.f2.ctr;
+        const size_t tk_keys = b.f2.tk;
         uint32_t* d_nrec = reinterpret_cast<uint32_t*>(ctr + 8);
-        const uint32_t* gtab = b.f2_tri_tab.as<uint32_t>();
+        const uint32_t* gtab = b.f2.tri_tab.as<uint32_t>();
         const uint32_t* gr = gtab + F;
-        // count + frequent pairs (a retry when the first record buffer was too small)
-        // the records land in mapped pinned host memory, the counts in pinned slots: one sync
-        uint32_t cap_recs = uint32_t(std::min<uint64_t>(uint64_t(rhi - rlo) * 2 * F, uint64_t(1) << 20));
+        // count + frequent pairs: the records land in mapped pinned host memory, the counts in
+        // pinned slots: one sync
         size_t tk_cnt = 0;
-        unsigned long long nkeys = 0;
-        for (int attempt = 0;; ++attempt) {
-            PinnedBuf* pb = ctx->pinned_big(size_t(std::max<uint32_t>(cap_recs, 1)) * sizeof(FreqRec));
-            if (attempt > 0) FSM_HIP(hipMemsetAsync(d_nrec, 0, 4, s));
-            tk_cnt = clk->begin("k_f2_count");
-            hipLaunchKernelGGL((k_f2_count<false, true>), dim3(G), dim3(kF2Threads), 0, s, base.as<uint64_t>(),
-                               fill.as<uint32_t>(), nblk, keys.as<uint16_t>(), 2 * F, 0u, 0u, rlo, rhi, minsup,
-                               static_cast<FreqRec*>(pb->dev), cap_recs, d_nrec, (uint32_t*)nullptr, 1u,
-                               gr, F);
-            FSM_LAUNCHED("k_f2_count", s);
-            clk->end(tk_cnt, int64_t(G) * nblk * 12);
-            pend[2] = pend[3] = 0;
-            FSM_HIP(hipMemcpyAsync(&pend[2], ctr, 16, hipMemcpyDeviceToHost, s));  // (one copy: both counts)
-            sync();
-            nkeys = pend[2];
-            const uint32_t nrec = uint32_t(pend[3] & 0xFFFFFFFFu);
-            if (nrec <= cap_recs || attempt > 0) {
-                if (nrec > cap_recs) throw Error(FSM_EDEVICE, "SPADE root F2: frequent pair buffer overflow");
-                const FreqRec* hr = static_cast<const FreqRec*>(pb->host);
-                double tr = now_ms();
-                if (b.f2_tri && F < (1u << 15) && order_device(b, pb, nrec, F, RkRows{nullptr, nullptr, F}, 2 * F, 2 * size_t(F) + 1)) {
-                    recs.clear();
-                    lap(14, tr);
-                    clk->add_bytes(tk_keys, int64_t(nkeys) * 2);
-                    clk->add_bytes(tk_cnt, int64_t(nkeys) * 2 + int64_t(nrec) * int64_t(sizeof(FreqRec)));
-                    ctx->stats.root_keys += int64_t(nkeys);
-                    return true;
-                }
-                recs.assign(hr, hr + nrec);
-                lap(14, tr);
-                break;
-            }
-            cap_recs = nrec;
-        }
-        clk->add_bytes(tk_keys, int64_t(nkeys) * 2);
-        clk->add_bytes(tk_cnt, int64_t(nkeys) * 2 + int64_t(recs.size() * sizeof(FreqRec)));
-        ctx->stats.root_keys += int64_t(nkeys);
-        const double th0 = now_ms();
-        double to_ = now_ms();
-        order_recs(recs, F, &rec_off_s);
-        lap(15, to_);
-        rec_off_ok = true;
-        hp[0] += now_ms() - th0;
+        PinnedBuf* pb = nullptr;
+        const uint32_t nrec = extract_capped(
+            uint32_t(std::min<uint64_t>(uint64_t(rhi - rlo) * 2 * F, uint64_t(1) << 20)),
+            "SPADE root F2: frequent pair buffer overflow", [&](uint32_t cap, bool retry) {
+                pb = ctx->pinned_big(size_t(std::max<uint32_t>(cap, 1)) * sizeof(FreqRec));
+                if (retry) FSM_HIP(hipMemsetAsync(d_nrec, 0, 4, s));
+                tk_cnt = clk->begin("k_f2_count");
+                hipLaunchKernelGGL((k_f2_count<false, true>), dim3(G), dim3(kF2Threads), 0, s, base.as<uint64_t>(),
+                                   fill.as<uint32_t>(), nblk, keys.as<uint16_t>(), 2 * F, 0u, 0u, rlo, rhi, minsup,
+                                   static_cast<FreqRec*>(pb->dev), cap, d_nrec, (uint32_t*)nullptr, 1u, gr, F);
+                FSM_LAUNCHED("k_f2_count", s);
+                clk->end(tk_cnt, int64_t(G) * nblk * 12);
+                return read_f2_counts(ctr);
+            });
+        root_f2_account(tk_keys, tk_cnt, nrec);
+        double tr = now_ms();
+        const bool on_device =
+            F < (1u << 15) && order_device(b, pb, nrec, F, RkRows{nullptr, nullptr, F}, 2 * F, 2 * size_t(F) + 1);
+        const FreqRec* hr = static_cast<const FreqRec*>(pb->host);
+        if (on_device) recs.clear();
+        else recs.assign(hr, hr + nrec);
+        lap(kLapF2Recs, tr);
+        if (!on_device) order_root_recs(recs, F);
         return true;
-    }
-    // FSM_DEVORDER=0: a batch's records ordered on the host (A/B)
-    static bool devorder_env() {  // (read per batch: the tests switch it within one process)
-        const char* v = std::getenv("FSM_DEVORDER");
-        return !(v && v[0] == '0');
     }
     // A batch's nrec frequent records (unordered, mapped pinned memory pb) ordered on the device
     // with the kid table [koff: nko | kslot | kcid] and the child-class table (k_rk_*), written
-    // back into pb in order (event b.rec_ev), and the batch set up for a deferred emit whose slab
+    // back into pb in order (event b.gpu.rec_ev), and the batch set up for a deferred emit whose slab
     // is sized by every record's support (the lone itemset extensions' entries are counted out
     // when the children are built).  rr: the counter rows (nrows), dmax: the largest member id
     // space of a row's class.  false: the host orders them (sharded, claims, over budget).
     bool order_device(Batch& b, PinnedBuf* pb, uint32_t nrec, uint32_t nrows, RkRows rr, uint32_t dmax, size_t nko) {
-        if (comm || nrec == 0 || nrows == 0 || !devorder_env() || defer_env() == 0 || b.claim_key >= 0 ||
+        if (comm || nrec == 0 || nrows == 0 || !knobs.devorder || !knobs.emit_defer || b.claim.key >= 0 ||
             dmax >= (1u << 16) || nko >= kNone)
             return false;
         const FreqRec* hr = static_cast<const FreqRec*>(pb->host);
@@ -3296,16 +3330,16 @@ struct Miner {
         FreqRec* R = static_cast<FreqRec*>(pb->dev);
         DevBuf Rd(size_t(n) * sizeof(FreqRec)), rowcnt(size_t(nrows) * 4), rowoff(size_t(nrows + 1) * 4),
             idx(size_t(n) * 4);
-        b.kid_tab.alloc((nko + 2 * size_t(n)) * 4);
-        b.ord_child_of.alloc(std::max<size_t>(nko - 1, 1) * 4);
+        b.gpu.kid_tab.alloc((nko + 2 * size_t(n)) * 4);
+        b.gpu.ord_child_of.alloc(std::max<size_t>(nko - 1, 1) * 4);
         uint32_t* cnt = rowcnt.as<uint32_t>();  // row counts | kRkEven
         FSM_HIP(hipMemsetAsync(cnt, 0, size_t(nrows) * 4, s));
         const unsigned gn = unsigned(std::min<uint64_t>((uint64_t(n) + kBlock - 1) / kBlock, 1024));
         hipLaunchKernelGGL(k_rk_hist, dim3(gn), dim3(kBlock), 0, s, R, n, Rd.as<FreqRec>(), cnt);
         FSM_LAUNCHED("k_rk_hist", s);
-        uint32_t* koff = b.kid_tab.as<uint32_t>();
+        uint32_t* koff = b.gpu.kid_tab.as<uint32_t>();
         hipLaunchKernelGGL(k_rk_tables, dim3((nrows + kRkTile - 1) / kRkTile), dim3(kBlock), 0, s, cnt, nrows, rr,
-                           uint32_t(nko), rowoff.as<uint32_t>(), koff, b.ord_child_of.as<uint32_t>());
+                           uint32_t(nko), rowoff.as<uint32_t>(), koff, b.gpu.ord_child_of.as<uint32_t>());
         FSM_LAUNCHED("k_rk_tables", s);
         hipLaunchKernelGGL(k_rk_scatter, dim3(gn), dim3(kBlock), 0, s, Rd.as<FreqRec>(), n, rowoff.as<uint32_t>(), cnt,
                            idx.as<uint32_t>());
@@ -3317,36 +3351,106 @@ struct Miner {
         hipLaunchKernelGGL(k_rk_row, dim3(nrows), dim3(kBlock), lds, s, Rd.as<FreqRec>(), idx.as<uint32_t>(),
                            rowoff.as<uint32_t>(), rr, nwmax, R, koff + nko, koff + nko + n);
         FSM_LAUNCHED("k_rk_row", s);
-        if (!b.rec_ev) FSM_HIP(hipEventCreateWithFlags(&b.rec_ev, hipEventDisableTiming));
-        FSM_HIP(hipEventRecord(b.rec_ev, s));
-        b.kid_off = b.kid_tab.as<uint32_t>();
-        b.kid_slot = b.kid_off + nko;
-        b.kid_cid = b.kid_slot + n;
-        b.child_of_pre = b.ord_child_of.as<uint32_t>();
+        if (!b.gpu.rec_ev.ev) FSM_HIP(hipEventCreateWithFlags(&b.gpu.rec_ev.ev, hipEventDisableTiming));
+        FSM_HIP(hipEventRecord(b.gpu.rec_ev.ev, s));
+        b.gpu.kid_off = b.gpu.kid_tab.as<uint32_t>();
+        b.gpu.kid_slot = b.gpu.kid_off + nko;
+        b.gpu.kid_cid = b.gpu.kid_slot + n;
+        b.defer.child_of = b.gpu.ord_child_of.as<uint32_t>();
         b.dev_order = true;
-        b.defer_children = true;
-        b.defer_R = hr;
-        b.defer_n = nrec;
-        b.defer_total = sumsup;  // (an upper bound: emit() counts the children's entries exactly)
-        b.defer_rows = &rows_s;
+        b.defer.on = true;
+        b.defer.R = hr;
+        b.defer.n = nrec;
+        b.defer.total = sumsup;  // (an upper bound: emit() counts the children's entries exactly)
+        b.defer.rows = &rows_s;
         b.children.clear();
         b.groups.assign(1, {size_t(0), size_t(0)});  // (the child count: set by emit())
         b.next_group = 0;
         return true;
     }
 
-    // The children loop of count_and_freq split over host threads (unsharded, large
-    // batches; same tables, same node ids: node of record q = first + q).  Every step
-    // runs over the same host-thread slices: row groups of the records (counts, then
-    // positions) -> per-group sizes and per-slice sums -> slice bases -> fill, each
-    // slice initialising its own ranges of the member tables.
+    // member ranks of the child class the records [q0, q1) of one row open (child ids: rank << 1 | type)
+    static uint32_t child_ranks(const FreqRec* R, uint64_t q0, uint64_t q1) {
+        uint32_t maxcid = 0;
+        for (uint64_t q = q0; q < q1; ++q) maxcid = std::max(maxcid, R[q].cid);
+        return (maxcid >> 1) + 1;
+    }
+    // The child class the records [q0, q1) of one row open, for both child builders: ch (a
+    // fresh record: its header and sums), its r ranks of the member tables at child_rank_item[ri] and
+    // child_node_of[2 ri], the records' pattern nodes at first + q (all sized by the caller).
+    // Returns the children's id-list bytes; ok is cleared when the parent pattern is at the
+    // item limit.
+    int64_t fill_child_class(Batch& b, const FreqRec* R, uint64_t q0, uint64_t q1, const RawVec<DRow>& rows, uint32_t r,
+                             uint64_t ri, size_t first, ChildInfo& ch, bool& ok) {
+        const DRow pr = rows[R[q0].row];
+        const ClassMeta& pm = b.cls[pr.cls];
+        const int32_t parent = b.node_of[pm.no_off + pr.mi];
+        const uint32_t pls = nodes[size_t(parent)].len_sets;
+        if ((pls >> 16) >= 0xFFFFu) ok = false;
+        ch.pcls = pr.cls;
+        ch.pmi = pr.mi;
+        ch.D = 2 * r;
+        ch.ri_off = ri;
+        ch.no_off = 2 * ri;
+        ch.psup = nodes[size_t(parent)].support;
+        std::fill_n(b.child_rank_item.data() + ri, r, 0u);
+        std::fill_n(b.child_node_of.data() + 2 * ri, 2 * r, -1);
+        int64_t bytes = 0;
+        for (uint64_t q = q0; q < q1; ++q) {
+            const FreqRec& fr = R[q];
+            const uint32_t item = b.rank_item[pm.ri_off + (fr.slot >> 1)];
+            const size_t node = first + q;
+            nodes[node] = PNode{parent, item, fr.slot & 1u, fr.sup, pls + (1u << 16) + ((fr.slot & 1u) == kSeq)};
+            b.child_rank_item[ch.ri_off + (fr.cid >> 1)] = item;
+            b.child_node_of[ch.no_off + fr.cid] = int32_t(node);
+            ch.cap += fr.sup;
+            if ((fr.slot & 1u) == kSeq) { ++ch.nS; ch.sS += fr.sup; } else { ++ch.nI; ch.sI += fr.sup; }
+            bytes += int64_t(12ull * fr.sup);
+        }
+        return bytes;
+    }
+
+    // the children of a counted batch (new pattern nodes, the next batch's class records and
+    // member tables) in deterministic (row, slot) order: the node of record q is first + q
+    void make_children(Batch& b, const FreqRec* R, uint64_t nfreq, const RawVec<DRow>& rows) {
+        b.children.clear();
+        b.child_rank_item.clear();
+        b.child_node_of.clear();
+        b.children.reserve(nfreq);
+        b.child_rank_item.reserve(nfreq + 16);
+        b.child_node_of.reserve(2 * nfreq + 16);
+        if (!comm && nfreq >= knobs.host_par_min) return children_parallel(b, R, nfreq, rows);
+        const size_t first = nodes.size();
+        for_row_groups(R, nfreq, 0, nfreq, [&](uint64_t q0, uint64_t q1) {
+            const uint32_t r = child_ranks(R, q0, q1);
+            const uint64_t ri = b.child_rank_item.size();
+            b.child_rank_item.resize(ri + r);
+            b.child_node_of.resize(2 * (ri + r));
+            nodes.grow(q1 - q0);
+            ChildInfo ch;
+            bool ok = true;
+            const int64_t bytes = fill_child_class(b, R, q0, q1, rows, r, ri, first, ch, ok);
+            if (!ok) throw Error(FSM_ELIMIT, "SPADE: a pattern exceeds 65534 items");
+            if (comm && b.cls[ch.pcls].split && comm->rank() != 0) {  // a split class's nodes: rank 0 outputs them
+                node_dup.resize(first + q0, 0);
+                node_dup.resize(first + q1, 1);
+            } else {
+                ctx->stats.bytes_join_equiv += bytes;
+            }
+            if (opens_class(R, q0, q1)) b.children.push_back(ch);
+        });
+    }
+    // The same over host threads (unsharded, from FSM_HOST_PAR_MIN records; same tables,
+    // same node ids).  Every step runs over the same host-thread slices: row groups of the
+    // records (counts, then positions) -> per-group sizes and per-slice sums -> slice bases
+    // -> fill, each slice initialising its own ranges of the member tables.
     void children_parallel(Batch& b, const FreqRec* R, uint64_t nfreq, const RawVec<DRow>& rows) {
         double tl = now_ms();
         const int64_t nthr = host_threads();
         std::vector<int64_t> tg(size_t(nthr) + 1, 0);
         par_slices(nthr, int64_t(nfreq), [&](int64_t t, int64_t q0, int64_t q1) {
             int64_t c = 0;
-            for (int64_t q = q0; q < q1; ++q) c += q == 0 || R[q].row != R[q - 1].row;
+            for_row_groups(R, nfreq, uint64_t(q0), uint64_t(q1), [&](uint64_t, uint64_t) { ++c; });
             tg[size_t(t) + 1] = c;
         });
         for (int64_t t = 0; t < nthr; ++t) tg[size_t(t) + 1] += tg[size_t(t)];
@@ -3355,24 +3459,19 @@ struct Miner {
         gs.resize(size_t(ng) + 1);
         par_slices(nthr, int64_t(nfreq), [&](int64_t t, int64_t q0, int64_t q1) {
             int64_t at = tg[size_t(t)];
-            for (int64_t q = q0; q < q1; ++q)
-                if (q == 0 || R[q].row != R[q - 1].row) gs[size_t(at++)] = uint64_t(q);
+            for_row_groups(R, nfreq, uint64_t(q0), uint64_t(q1), [&](uint64_t g0, uint64_t) { gs[size_t(at++)] = g0; });
         });
         gs[size_t(ng)] = nfreq;
-        lap(0, tl);
-        // r2: member ranks of each group's child (bit 31: the child is kept; a lone
-        // itemset-extension opens no class)
+        lap(kLapRowGroups, tl);
+        // r2: member ranks of each group's child (bit 31: the child is kept)
         RawVec<uint32_t>& r2 = r2_s;
         r2.resize(size_t(ng));
         std::vector<uint64_t> tri(size_t(nthr) + 1, 0), tk(size_t(nthr) + 1, 0);
         par_slices(nthr, ng, [&](int64_t t, int64_t i0, int64_t i1) {
             uint64_t sri = 0, sk = 0;
             for (int64_t i = i0; i < i1; ++i) {
-                uint32_t maxcid = 0;
-                for (uint64_t q = gs[size_t(i)]; q < gs[size_t(i) + 1]; ++q) maxcid = std::max(maxcid, R[q].cid);
-                const uint32_t r = (maxcid >> 1) + 1;
-                const uint64_t nch = gs[size_t(i) + 1] - gs[size_t(i)];
-                const bool keep = !(nch == 1 && (R[gs[size_t(i)]].slot & 1u) == kItm);
+                const uint32_t r = child_ranks(R, gs[size_t(i)], gs[size_t(i) + 1]);
+                const bool keep = opens_class(R, gs[size_t(i)], gs[size_t(i) + 1]);
                 r2[size_t(i)] = r | (keep ? 0x80000000u : 0u);
                 sri += r;
                 sk += keep;
@@ -3384,451 +3483,504 @@ struct Miner {
             tri[size_t(t) + 1] += tri[size_t(t)];
             tk[size_t(t) + 1] += tk[size_t(t)];
         }
-        lap(1, tl);
+        lap(kLapChildSizes, tl);
         b.child_rank_item.resize(tri[size_t(nthr)]);
         b.child_node_of.resize(2 * tri[size_t(nthr)]);
         b.children.resize(tk[size_t(nthr)]);
-        const size_t node0 = nodes.size();
+        const size_t first = nodes.size();
         nodes.grow(nfreq);
-        lap(3, tl);
+        lap(kLapChildAlloc, tl);
         std::vector<int64_t> jb(size_t(nthr), 0);
-        std::vector<int> bad(size_t(nthr), 0);
+        std::vector<uint8_t> good(size_t(nthr), 1);
         par_slices(nthr, ng, [&](int64_t t, int64_t i0, int64_t i1) {
             int64_t acc = 0;
+            bool ok = true;
             uint64_t ri = tri[size_t(t)], kidx = tk[size_t(t)];
             for (int64_t i = i0; i < i1; ++i) {
-                const uint64_t q0 = gs[size_t(i)], q1 = gs[size_t(i) + 1];
                 const uint32_t r = r2[size_t(i)] & 0x7FFFFFFFu;
-                const DRow pr = rows[R[q0].row];
-                const ClassMeta& pm = b.cls[pr.cls];
-                const int32_t parent = b.node_of[pm.no_off + pr.mi];
-                const uint32_t pls = nodes[size_t(parent)].len_sets;
-                if ((pls >> 16) >= 0xFFFFu) bad[size_t(t)] |= 1;
                 ChildInfo ch;
-                ch.pcls = pr.cls;
-                ch.pmi = pr.mi;
-                ch.D = 2 * r;
-                ch.ri_off = ri;
-                ch.no_off = 2 * ri;
-                ch.psup = nodes[size_t(parent)].support;
-                std::fill_n(b.child_rank_item.data() + ri, r, 0u);
-                std::fill_n(b.child_node_of.data() + 2 * ri, 2 * r, -1);
-                for (uint64_t q = q0; q < q1; ++q) {
-                    const FreqRec& fr = R[q];
-                    const uint32_t item = b.rank_item[pm.ri_off + (fr.slot >> 1)];
-                    const size_t node = node0 + q;
-                    nodes[node] = PNode{parent, item, fr.slot & 1u, fr.sup, pls + (1u << 16) + ((fr.slot & 1u) == kSeq)};
-                    b.child_rank_item[ch.ri_off + (fr.cid >> 1)] = item;
-                    b.child_node_of[ch.no_off + fr.cid] = int32_t(node);
-                    ch.cap += fr.sup;
-                    if ((fr.slot & 1u) == kSeq) { ++ch.nS; ch.sS += fr.sup; } else { ++ch.nI; ch.sI += fr.sup; }
-                    acc += int64_t(12ull * fr.sup);
-                }
+                acc += fill_child_class(b, R, gs[size_t(i)], gs[size_t(i) + 1], rows, r, ri, first, ch, ok);
                 ri += r;
                 if (r2[size_t(i)] >> 31) b.children[kidx++] = ch;
             }
             jb[size_t(t)] = acc;
+            good[size_t(t)] = ok;
         });
-        lap(4, tl);
+        lap(kLapChildFill, tl);
         for (int64_t t = 0; t < nthr; ++t) {
-            if (bad[size_t(t)] & 1) throw Error(FSM_ELIMIT, "SPADE: a pattern exceeds 65534 items");
+            if (!good[size_t(t)]) throw Error(FSM_ELIMIT, "SPADE: a pattern exceeds 65534 items");
             ctx->stats.bytes_join_equiv += jb[size_t(t)];
         }
     }
 
-    // count kernel + frequent-candidate extraction; fills b.children / b.groups / kids
+    // FSM_HOST_TRACE=2: one line per batch with its host phases (diagnostics)
+    struct BatchTrace {
+        const Miner& m;
+        const Batch& b;
+        double t0, h0[kPhases];
+        BatchTrace(const Miner& m_, const Batch& b_, double t0_) : m(m_), b(b_), t0(t0_) {
+            std::copy(m.hp, m.hp + kPhases, h0);
+        }
+        ~BatchTrace() {
+            std::fprintf(stderr, "[fsm batch] depth %lld root %d E %llu classes %zu children %zu: %.3f ms (", (long long)b.depth,
+                         int(b.root), (unsigned long long)b.E, b.cls.size(), b.children.size(), now_ms() - t0);
+            for (int i = 0; i < kPhases; ++i) std::fprintf(stderr, " %.3f", m.hp[i] - h0[i]);
+            std::fprintf(stderr, " )\n");
+        }
+    };
+    // which count ran for a batch (count), and the frequent records it left (extract)
+    enum class CountPath { kRootF2, kSparse, kKeyed, kAtomic };
+    struct Records {
+        const FreqRec* R = nullptr;  // in (row, slot) order with their child member ids; valid until the next batch
+        uint64_t n = 0;
+        bool kids_on_device = false;     // the kid table is in b.gpu.kid_tab already (k_freq_write + k_kid_off)
+        bool row_offsets = false;        // rec_off_s holds their row offsets over every counter row
+        bool ordered_on_device = false;  // order_device took them: kid table and children deferred to emit()
+    };
+
+    // One batch, stage by stage: count its candidate joins, extract the frequent ones as
+    // records, build the kid table the emit kernels read, and either hand the records to
+    // emit() (deferred children: one group, unsharded) or build the children, plan the
+    // first level over the ranks (sharded) and pack them into emit groups.
     void count_and_freq(Batch& b) {
         const double tc0 = now_ms();
-        rec_off_ok = false;
-        double tl = tc0;
-        // FSM_HOST_TRACE=2: one line per batch with its host phases (diagnostics)
-        struct BatchTrace {
-            Miner* m;
-            Batch* b;
-            double h0[8], t0;
-            ~BatchTrace() {
-                std::fprintf(stderr, "[fsm batch] depth %lld root %d E %llu classes %zu children %zu: %.3f ms (", (long long)b->depth,
-                             int(b->root), (unsigned long long)b->E, b->cls.size(), b->children.size(), now_ms() - t0);
-                for (int i = 0; i < 8; ++i) std::fprintf(stderr, " %.3f", m->hp[i] - h0[i]);
-                std::fprintf(stderr, " )\n");
-            }
-        };
-        static const bool btrace = [] { const char* v = std::getenv("FSM_HOST_TRACE"); return v && v[0] == '2'; }();
-        std::unique_ptr<BatchTrace> bt;
-        if (btrace) {
-            bt = std::make_unique<BatchTrace>();
-            bt->m = this;
-            bt->b = &b;
-            for (int i = 0; i < 8; ++i) bt->h0[i] = hp[i];
-            bt->t0 = tc0;
-        }
+        std::optional<BatchTrace> bt;
+        if (knobs.host_trace == 2) bt.emplace(*this, b, tc0);
         dump(b);
+        double tl = tc0;
         const int cmode = count_mode(b);
-        lap(5, tl);
+        lap(kLapCountMode, tl);
         const bool keyed_layout = prepare(b, cmode != 0);
-        lap(6, tl);
+        lap(kLapPrepare, tl);
+        batch_stats(b);
+        lap(kLapStats, tl);
+        member_rows(b);
+        lap(kLapRows, tl);
+        hp[kCountPrep] += now_ms() - tc0;
+        const double tc1 = now_ms();
         const bool shard = comm && b.root;  // root rows split over ranks, frequent pairs all-gathered
+        Records recs;
+        auto count_extract = [&] {
+            DevBuf cnt;
+            const CountPath path = count(b, keyed_layout, cnt);
+            recs = extract(b, path, cnt);
+        };
+        if (shard) run_or_defer(count_extract);  // a failure here or in run_root reaches every rank in the gather
+        else count_extract();
+        hp[kCountExtract] += now_ms() - tc1;  // device count + extraction + ordering (incl. waits)
+        if (shard) recs = gather_sharded(b, recs);
+        if (recs.ordered_on_device) return;  // kid and child-class tables built on the device; emit() builds the children
+        // deferred children: emit() builds them after launching its kernels.  A host-built kid
+        // table carries the deferred emit's child_of table, so it needs the decision first
+        double th = now_ms();
+        bool defer = !recs.kids_on_device && defer_ok(b, recs);
+        build_kid_table(b, recs, defer);
+        hp[kKids] += now_ms() - th;
+        th = now_ms();
+        if (recs.kids_on_device) defer = defer_ok(b, recs);
+        if (!defer) {
+            make_children(b, recs.R, recs.n, rows_s);
+            plan_first_level(b);
+        }
+        hp[kChildren] += now_ms() - th;
+        if (defer) return;
+        th = now_ms();
+        pack_groups(b);
+        hp[kGroups] += now_ms() - th;
+        if (ctx->opts.verbose && b.claim.key < 0)
+            std::fprintf(stderr, "[fsm] batch: classes=%zu entries=%llu freq=%llu children=%zu groups=%zu\n",
+                         b.cls.size(), (unsigned long long)b.E, (unsigned long long)recs.n, b.children.size(),
+                         b.groups.size());
+    }
+
+    // the batch's work counters
+    void batch_stats(const Batch& b) {
+        fsm_stats& st = ctx->stats;
         const int64_t ncls = int64_t(b.cls.size());
         const int64_t nthr = ncls >= (int64_t(1) << 15) ? host_threads() : 1;
-        // the root and split classes are counted by every rank: their stats come from rank 0
+        ClassStats sum;
+        int64_t counted = 0;
         if (comm || nthr == 1) {
-            for (auto& m : b.cls)
-                if (!comm || (!shard && !m.split) || comm->rank() == 0) stats_for_class(b, m);
-        } else {  // unsharded, many classes: the same sums over host threads
-            std::vector<int64_t> sj(size_t(nthr), 0), sb(size_t(nthr), 0);
-            par_slices(nthr, ncls, [&](int64_t t, int64_t c0, int64_t c1) {
-                int64_t j = 0, bb = 0;
-                for (int64_t c = c0; c < c1; ++c) {
-                    const ClassMeta& m = b.cls[size_t(c)];
-                    const uint64_t S = m.nS, I = m.nI, sS = m.sS, sI = m.sI;
-                    j += int64_t(S * S + I * S + (S ? S * (S - 1) / 2 : 0) + (I ? I * (I - 1) / 2 : 0));
-                    bb += int64_t(12 * (2 * S * sS + S * sI + I * sS + (S ? (S - 1) * sS : 0) + (I ? (I - 1) * sI : 0)));
+            // the root and split classes are counted by every rank: their stats come from rank 0
+            const bool shard = comm && b.root;
+            for (const ClassMeta& m : b.cls)
+                if (!comm || (!shard && !m.split) || comm->rank() == 0) {
+                    sum += class_stats(m);
+                    ++counted;
                 }
-                sj[size_t(t)] = j;
-                sb[size_t(t)] = bb;
+        } else {  // unsharded, many classes: the same sums over host threads
+            std::vector<ClassStats> ts(static_cast<size_t>(nthr));
+            par_slices(nthr, ncls, [&](int64_t t, int64_t c0, int64_t c1) {
+                ClassStats a;  // (summed locally: the slices' slots share cache lines)
+                for (int64_t c = c0; c < c1; ++c) a += class_stats(b.cls[size_t(c)]);
+                ts[size_t(t)] = a;
             });
-            for (int64_t t = 0; t < nthr; ++t) {
-                ctx->stats.joins += sj[size_t(t)];
-                if (b.root) ctx->stats.joins_root += sj[size_t(t)];
-                ctx->stats.bytes_join_equiv += sb[size_t(t)];
-            }
-            ctx->stats.classes += ncls;
+            for (const ClassStats& t : ts) sum += t;
+            counted = ncls;
         }
-        lap(7, tl);
-        fsm_stats& st = ctx->stats;
+        st.joins += sum.joins;
+        if (b.root) st.joins_root += sum.joins;
+        st.bytes_join_equiv += sum.bytes;
+        st.classes += counted;
         st.batches += 1;
-        const uint64_t tot_ent = b.E;
-        st.entries += int64_t(tot_ent);
-        st.bytes_streamed += int64_t(tot_ent * entry_bytes());
-        st.bytes_count_alg += int64_t(tot_ent * entry_bytes());
-        // member rows of the counter matrix
+        st.entries += int64_t(b.E);
+        st.bytes_streamed += int64_t(b.E * entry_bytes());
+        st.bytes_count_alg += int64_t(b.E * entry_bytes());
+    }
+
+    // member rows of the counter matrix (rows_s): every member of every class, in class order
+    void member_rows(const Batch& b) {
         RawVec<DRow>& rows = rows_s;
         rows.clear();
+        const int64_t ncls = int64_t(b.cls.size());
+        const int64_t nthr = ncls >= (int64_t(1) << 15) ? host_threads() : 1;
         if (nthr == 1) {
             for (size_t c = 0; c < b.cls.size(); ++c)
                 for (uint32_t mi = 0; mi < b.cls[c].D; ++mi)
                     if (b.node_of[b.cls[c].no_off + mi] >= 0) rows.push_back(DRow{uint32_t(c), mi});
-        } else {  // a class's rows are its members (nS + nI of them): slice sums, then a parallel fill
-            std::vector<uint64_t> ro(size_t(nthr) + 1, 0);
-            par_slices(nthr, ncls, [&](int64_t t, int64_t c0, int64_t c1) {
-                uint64_t n = 0;
-                for (int64_t c = c0; c < c1; ++c) n += b.cls[size_t(c)].nS + b.cls[size_t(c)].nI;
-                ro[size_t(t) + 1] = n;
-            });
-            for (int64_t t = 0; t < nthr; ++t) ro[size_t(t) + 1] += ro[size_t(t)];
-            rows.resize(ro[size_t(nthr)]);
-            par_slices(nthr, ncls, [&](int64_t t, int64_t c0, int64_t c1) {
-                uint64_t at = ro[size_t(t)];
-                for (int64_t c = c0; c < c1; ++c) {
-                    const ClassMeta& m = b.cls[size_t(c)];
-                    for (uint32_t mi = 0; mi < m.D; ++mi)
-                        if (b.node_of[m.no_off + mi] >= 0) rows[at++] = DRow{uint32_t(c), mi};
-                }
-            });
-        }
-        // root rows are rows[r] = rank r: a shard extracts its own slice of them
-        const uint32_t rlo = shard ? std::min<uint32_t>(slice_lo, uint32_t(rows.size())) : 0u;
-        const uint32_t rhi = shard ? std::min<uint32_t>(slice_hi, uint32_t(rows.size())) : uint32_t(rows.size());
-        const uint32_t nrows = rhi - rlo;
-        std::vector<FreqRec>& recs = recs_s;
-        recs.clear();
-        const FreqRec* ext = nullptr;  // ordered extraction: the records in pinned host memory
-        uint64_t ext_n = 0;
-        bool kids_dev = false;  // the kid table was built on the device (k_freq_write + k_kid_off)
-        DevBuf cnt;
-        lap(8, tl);
-        hp[6] += now_ms() - tc0;  // prepare + stats + rows
-        const double tc1 = now_ms();
-        auto compute = [&] {
-        // the root: pairs counted per rank group, only the frequent ones leave the device
-        const bool root_done = b.E && b.root && !root_atomic() && root_f2(b, recs);
-        if (b.db_direct && b.E && !root_done)
-            throw Error(FSM_EDEVICE, "SPADE internal error: the DB-direct root F2 did not apply");
-        if (b.E) st.count_launches += 1;
-        // huge, sparse counter matrices: the joins sorted instead (records in (row, slot) order)
-        const bool sparse_done = !root_done && b.E && sparse_wanted(b) && sparse_count(b, recs, rows);
-        if (sparse_done) {
-            order_recs(recs, uint32_t(rows.size()), &rec_off_s);
-            rec_off_ok = true;
             return;
         }
-        const bool keyed_done = !root_done && keyed_layout && keyed_count(b, cnt);
-        uint32_t* d_nz = nullptr;  // a zeroed u32 after the counters (the extraction's record count)
-        if (!root_done && !keyed_done) {
-            cnt.alloc((b.n_cnt + 1) * 4);
-            FSM_HIP(hipMemsetAsync(cnt.p, 0, (b.n_cnt + 1) * 4, s));
-            d_nz = cnt.as<uint32_t>() + b.n_cnt;
-        }
-        if (!root_done) {
-            if (b.E && !keyed_done) {
-                const SlabPtrs sp = b.slab.ptrs();
-                const uint32_t cchunk = count_chunk();
-#define FSM_COUNT(WW)                                                                                   \
-    hipLaunchKernelGGL(k_count<WW>, dim3(unsigned((b.E + cchunk - 1) / cchunk)), dim3(kBlock), 0, s,   \
-                       uint32_t(b.E), sp.cid, b.d_cls.as<DClass>(), sp.mem, sp.lohi, sp.pos, sp.mask,           \
-                       member_lo(b), member_hi(b), cchunk, cnt.as<uint32_t>(), d_tests,    \
-                       uint32_t(W))
-                const size_t tk = clk->begin("k_count");
-                if ((W == 1 || W == 2 || W == 4 || W == 8) && count_window()) {
-                    const unsigned g = unsigned(std::min<uint64_t>((b.E + 4 * kC2Range - 1) / (4 * kC2Range), 1u << 16));
-#define FSM_COUNT2(WW)                                                                                  \
-    hipLaunchKernelGGL(k_count2<WW>, dim3(g), dim3(kBlock), 0, s, uint32_t(b.E), sp.cid, b.d_cls.as<DClass>(), \
-                       sp.mem, sp.lohi, sp.pos, sp.mask, member_lo(b), member_hi(b), cnt.as<uint32_t>(),      \
-                       d_tests)
-                    switch (W) {
-                        case 1: FSM_COUNT2(1); break;
-                        case 2: FSM_COUNT2(2); break;
-                        case 4: FSM_COUNT2(4); break;
-                        default: FSM_COUNT2(8); break;
-                    }
-#undef FSM_COUNT2
-                } else {
-                    FSM_W_DISPATCH(W, FSM_COUNT)
-                }
-#undef FSM_COUNT
-                FSM_LAUNCHED("k_count", s);
-                clk->end(tk, int64_t(b.E * entry_bytes() + b.n_cnt * 4), int64_t(b.E * survey_entry_bytes()));
-            }
-            DevBuf d_rows;
-            upload_staged(1, d_rows, rows.data() + rlo, size_t(nrows) * sizeof(DRow));
-            const unsigned grid = unsigned((uint64_t(nrows) * 64 + kBlock - 1) / kBlock);
-            if (nrows > kFreqOnePassRows) {
-                // large batches: ordered extraction (the host ordering and the mapped-memory
-                // reads of millions of records cost more than the extra sync)
-                DevBuf rowcnt((size_t(nrows) + 1) * 4), rowoff((size_t(nrows) + 1) * 8);
-                {
-                    const size_t tk = clk->begin("k_freq_count");
-                    hipLaunchKernelGGL(k_freq_count, dim3(grid), dim3(kBlock), 0, s, d_rows.as<DRow>(), nrows,
-                                       b.d_cls.as<DClass>(), cnt.as<uint32_t>(), minsup, rowcnt.as<uint32_t>());
-                    FSM_LAUNCHED("k_freq_count", s);
-                    clk->end(tk, int64_t(uint64_t(nrows) * (b.n_cnt / std::max<uint64_t>(rows.size(), 1)) * 4));
-                }
-                scan_exclusive(rowcnt.as<uint32_t>(), rowoff.as<uint64_t>(), nrows, s);
-                FSM_HIP(hipMemcpyAsync(&pend[1], rowoff.as<uint64_t>() + nrows, 8, hipMemcpyDeviceToHost, s));
-                sync();
-                const uint64_t nf = pend[1];
-                if (nf) {  // records straight into mapped pinned host memory, read there after the sync
-                    PinnedBuf* pb = ctx->pinned_big(nf * sizeof(FreqRec));
-                    // unsharded: the kid table [koff | kslot | kcid] is built here, in HBM
-                    const bool dk = !comm && !kids_host() && rlo == 0 && nrows == rows.size();
-                    const size_t nko = size_t(b.cbase_total) + 1;
-                    uint32_t *kslot = nullptr, *kcid = nullptr;
-                    if (dk) {
-                        b.kid_tab.alloc((nko + 2 * size_t(nf)) * 4);
-                        kslot = b.kid_tab.as<uint32_t>() + nko;
-                        kcid = kslot + nf;
-                    }
-                    const size_t tk = clk->begin("k_freq_write");
-                    hipLaunchKernelGGL(k_freq_write, dim3(grid), dim3(kBlock), 0, s, d_rows.as<DRow>(), nrows,
-                                       b.d_cls.as<DClass>(), cnt.as<uint32_t>(), minsup, rowoff.as<uint64_t>(), rlo,
-                                       static_cast<FreqRec*>(pb->dev), kslot, kcid);
-                    FSM_LAUNCHED("k_freq_write", s);
-                    if (dk) {
-                        hipLaunchKernelGGL(k_kid_off, dim3(unsigned((nrows + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
-                                           d_rows.as<DRow>(), nrows, b.d_cls.as<DClass>(), rowoff.as<uint64_t>(),
-                                           uint32_t(nko), b.kid_tab.as<uint32_t>());
-                        FSM_LAUNCHED("k_kid_off", s);
-                        kids_dev = true;
-                    }
-                    clk->end(tk, int64_t(uint64_t(nrows) * (b.n_cnt / std::max<uint64_t>(rows.size(), 1)) * 4 +
-                                         nf * sizeof(FreqRec)));
-                    sync();
-                    ext = static_cast<const FreqRec*>(pb->host);
-                    ext_n = nf;
-                }
-                return;
-            }
-            // one pass, unordered records at block cursors; rare overflow: extract again at the exact size
-            uint32_t cap_recs = uint32_t(std::min<uint64_t>(std::max<uint64_t>(uint64_t(nrows) * 4, 4096), b.n_cnt));
-            // the records land in mapped pinned host memory: one stream sync per batch
-            DevBuf d_n;
-            uint32_t* dn = d_nz;  // zeroed with the counters (a retry or the keyed count: its own)
-            // the last emit's block has a zeroed counter for this count: both come back in one copy
-            const bool ride = pend_check && emit_blk && !emit_copied;
-            if (ride) dn = reinterpret_cast<uint32_t*>(emit_blk + 16);
-            for (int attempt = 0; nrows; ++attempt) {
-                PinnedBuf* pb = ctx->pinned_big(size_t(std::max<uint32_t>(cap_recs, 1)) * sizeof(FreqRec));
-                if (attempt > 0 || dn == nullptr) {
-                    if (d_n.p == nullptr) d_n.alloc(4);
-                    dn = d_n.as<uint32_t>();
-                    FSM_HIP(hipMemsetAsync(dn, 0, 4, s));
-                }
-                const size_t tk = clk->begin("k_freq_recs");
-                hipLaunchKernelGGL(k_freq_recs, dim3(grid), dim3(kBlock), 0, s, d_rows.as<DRow>(), nrows,
-                                   b.d_cls.as<DClass>(), cnt.as<uint32_t>(), minsup, rlo,
-                                   static_cast<FreqRec*>(pb->dev), cap_recs, dn);
-                FSM_LAUNCHED("k_freq_recs", s);
-                clk->end(tk, int64_t(uint64_t(nrows) * (b.n_cnt / std::max<uint64_t>(rows.size(), 1)) * 4));
-                uint32_t nf = 0;
-                if (ride && attempt == 0) {
-                    FSM_HIP(hipMemcpyAsync(&pend[8], emit_blk, 24, hipMemcpyDeviceToHost, s));
-                    emit_copied = true;
-                    sync();
-                    nf = uint32_t(pend[10] & 0xFFFFFFFFu);
-                } else {
-                    FSM_HIP(hipMemcpyAsync(&pend[1], dn, 4, hipMemcpyDeviceToHost, s));
-                    sync();
-                    nf = uint32_t(pend[1] & 0xFFFFFFFFu);
-                }
-                if (nf <= cap_recs) {
-                    // unsharded, one emit group: ordered on the device, the children deferred to emit()
-                    if (nf && rlo == 0 && nrows == rows.size() && !comm && !kids_host()) {
-                        uint32_t dmax = 0;
-                        for (const ClassMeta& m : b.cls) dmax = std::max(dmax, m.D);
-                        if (order_device(b, pb, nf, nrows, RkRows{d_rows.as<DRow>(), b.d_cls.as<DClass>(), 0u}, dmax,
-                                         size_t(b.cbase_total) + 1)) {
-                            recs.clear();
-                            return;
-                        }
-                    }
-                    const FreqRec* hr = static_cast<const FreqRec*>(pb->host);
-                    recs.assign(hr, hr + nf);
-                    break;
-                }
-                if (attempt > 0) throw Error(FSM_EDEVICE, "SPADE: frequent candidate buffer overflow");
-                cap_recs = nf;
-            }
-            order_recs(recs, rhi, &rec_off_s);
-            rec_off_ok = rhi == rows.size();
-        }
-        };
-        if (shard) {  // a failure here or in run_root reaches every rank in the gather below
-            run_or_defer(compute);
-        } else {
-            compute();
-        }
-        const FreqRec* R = ext ? ext : recs.data();
-        uint64_t nfreq = ext ? ext_n : recs.size();
-        cnt.release();
-        hp[7] += now_ms() - tc1;  // device count + extraction + ordering (incl. waits)
-        if (shard) {  // every rank gets every frequent pair, in row order (slices ascend with the rank)
-            if (agr.code) nfreq = 0;
-            std::vector<uint8_t> mine(nfreq * sizeof(FreqRec));
-            if (nfreq) std::memcpy(mine.data(), R, mine.size());
-            std::vector<size_t> sizes;
-            // the claim counter of this mine's first-level classes is reset before this gather
-            // (the collective every rank passes before its first claim); the same all-reduce
-            // carries the failure agreement and, at the first sharded mine, whether every rank
-            // has the shared counters
-            b.claim_key = comm->next_key();
-            comm->reset_counter(b.claim_key);
-            uint32_t ex = comm->has_fetch_add() && claims_env() ? 1u : 0u;
-            const std::vector<uint8_t> all = comm->gather_blobs(mine, sizes, s, &agr, &ex, 1);
-            if (comm->claim_mode < 0) comm->claim_mode = ex == uint32_t(comm->nranks()) ? 1 : 0;
-            nfreq = all.size() / sizeof(FreqRec);
-            recs.resize(nfreq);
-            if (nfreq) std::memcpy(recs.data(), all.data(), all.size());
-            // the unordered-pair F2 gives a rank records of rows above its slice: (row, slot)
-            // order and the child ids over the whole set.  Every rank orders them, whatever its
-            // own F2 layout (a rank with an empty slice runs the ordered one): the ranks must
-            // derive identical children, or their collective sequences part
-            order_recs(recs, uint32_t(rows.size()), &rec_off_s);
-            rec_off_ok = true;
-            R = recs.data();
-        }
-        double th = now_ms();
-        // kids CSR over (cbase + mi): the frequent children of every member, by slot
-        // one table, one H2D copy: [koff: cbase_total + 1 | kslot: nfreq | kcid: nfreq]
-        if (b.dev_order) {  // kid and child-class tables built on the device; emit() builds the children
-            hp[1] += now_ms() - th;
-            return;
-        }
-        const size_t nko = size_t(b.cbase_total) + 1;
-        bool defer_checked = false;
-        if (kids_dev) {
-            b.kid_off = b.kid_tab.as<uint32_t>();
-            b.kid_slot = b.kid_off + nko;
-            b.kid_cid = b.kid_slot + nfreq;
-        } else {
-        // deferred children (one group, unsharded; decided here, the children are built by emit()):
-        // the host child_of table (member slot -> child class) rides in the same upload
-        b.child_of_pre = nullptr;
-        double tl3 = now_ms();
-        const bool defer = defer_ok(b, R, nfreq, rows);
-        lap(12, tl3);
-        defer_checked = true;
-        const bool pre_co = defer && !child_of_device(b.cbase_total);
-        const size_t nco = pre_co ? size_t(b.cbase_total) : 0;
-        // the table is filled straight into the pinned staging slot it is DMA'd from
-        const size_t kbytes = (nko + 2 * size_t(nfreq) + nco) * 4;
-        uint32_t* koff = static_cast<uint32_t*>(ctx->stage_host(2, kbytes));
-        uint32_t* kslot = koff + nko;
-        uint32_t* kcid = kslot + nfreq;
-        double tl2 = th;
-        lap(9, tl2);
-        // records are in (row, slot) order, and a row's member slot cbase + mi ascends
-        // with the row: koff[x] = records of slots < x
-        const int64_t nthk = nfreq >= par_min() ? host_threads() : 1;
-        if (rec_off_ok && rec_off_s.size() == rows.size() + 1) {
-            // from the row offsets of the ordering: slots (s(r-1), s(r)] take off[r]
-            uint64_t x = 0;
-            for (size_t r = 0; r < rows.size(); ++r) {
-                const uint64_t sr = uint64_t(b.cls[rows[r].cls].cbase) + rows[r].mi;
-                const uint32_t o = rec_off_s[r];
-                for (; x <= sr && x < nko; ++x) koff[x] = o;
-            }
-            for (; x < nko; ++x) koff[x] = uint32_t(nfreq);
-        } else {  // (records ordered on the device: a merge, threads split x)
-            auto slot_of = [&](uint64_t q) { return uint64_t(b.cls[rows[R[q].row].cls].cbase) + rows[R[q].row].mi; };
-            par_slices(nthk, int64_t(nko), [&](int64_t, int64_t x0, int64_t x1) {
-                uint64_t lo = 0, hi = nfreq;  // first record with slot >= x0
-                while (lo < hi) {
-                    const uint64_t mid = (lo + hi) / 2;
-                    if (slot_of(mid) < uint64_t(x0)) lo = mid + 1; else hi = mid;
-                }
-                uint64_t q = lo;
-                for (int64_t x = x0; x < x1; ++x) {
-                    while (q < nfreq && slot_of(q) < uint64_t(x)) ++q;
-                    koff[x] = uint32_t(q);
-                }
-            });
-        }
-        par_slices(nthk, int64_t(nfreq), [&](int64_t, int64_t q0, int64_t q1) {
-            for (int64_t q = q0; q < q1; ++q) {  // recs are ordered by (row, slot) = CSR order
-                kslot[q] = R[q].slot;
-                kcid[q] = R[q].cid;
+        // a class's rows are its members (nS + nI of them): slice sums, then a parallel fill
+        std::vector<uint64_t> ro(size_t(nthr) + 1, 0);
+        par_slices(nthr, ncls, [&](int64_t t, int64_t c0, int64_t c1) {
+            uint64_t n = 0;
+            for (int64_t c = c0; c < c1; ++c) n += b.cls[size_t(c)].nS + b.cls[size_t(c)].nI;
+            ro[size_t(t) + 1] = n;
+        });
+        for (int64_t t = 0; t < nthr; ++t) ro[size_t(t) + 1] += ro[size_t(t)];
+        rows.resize(ro[size_t(nthr)]);
+        par_slices(nthr, ncls, [&](int64_t t, int64_t c0, int64_t c1) {
+            uint64_t at = ro[size_t(t)];
+            for (int64_t c = c0; c < c1; ++c) {
+                const ClassMeta& m = b.cls[size_t(c)];
+                for (uint32_t mi = 0; mi < m.D; ++mi)
+                    if (b.node_of[m.no_off + mi] >= 0) rows[at++] = DRow{uint32_t(c), mi};
             }
         });
-        lap(10, tl2);
-        if (pre_co) {  // the member slots that open a class, numbered in record order (as emit's)
-            uint32_t* co = kcid + nfreq;
-            std::fill(co, co + nco, kNone);
-            uint32_t k = 0;
-            for (uint64_t q = 0; q < nfreq;) {
-                uint64_t q2 = q;
-                while (q2 < nfreq && R[q2].row == R[q].row) ++q2;
-                if (!(q2 - q == 1 && (R[q].slot & 1u) == kItm)) {
-                    const DRow pr = rows[R[q].row];
-                    co[b.cls[pr.cls].cbase + pr.mi] = k++;
-                }
-                q = q2;
+    }
+    // root rows are rows[r] = rank r: a shard extracts its own slice [lo, hi) of them (else: every row)
+    std::pair<uint32_t, uint32_t> row_slice(const Batch& b) const {
+        const uint32_t n = uint32_t(rows_s.size());
+        if (!(comm && b.root)) return {0u, n};
+        return {std::min(slice_lo, n), std::min(slice_hi, n)};
+    }
+
+    // The count of a batch: the root F2 by rank groups (only the frequent pairs leave the
+    // device: recs_s), the sorted sparse count for huge matrices (recs_s too), the keyed
+    // count, or global atomics into cnt (k_count2 / k_count).
+    CountPath count(Batch& b, bool keyed_layout, DevBuf& cnt) {
+        recs_s.clear();
+        const bool root_done = b.E && b.root && !knobs.root_atomic && root_f2(b, recs_s);
+        if (b.db_direct && b.E && !root_done)
+            throw Error(FSM_EDEVICE, "SPADE internal error: the DB-direct root F2 did not apply");
+        if (b.E) ctx->stats.count_launches += 1;
+        if (root_done) return CountPath::kRootF2;
+        if (b.E && sparse_wanted(b) && sparse_count(b, recs_s, rows_s)) return CountPath::kSparse;
+        if (keyed_layout && keyed_count(b, cnt)) return CountPath::kKeyed;
+        // (one more zeroed u32 after the counters: the one-pass extraction's record count)
+        cnt.alloc((b.n_cnt + 1) * 4);
+        FSM_HIP(hipMemsetAsync(cnt.p, 0, (b.n_cnt + 1) * 4, s));
+        if (!b.E) return CountPath::kAtomic;
+        const SlabPtrs sp = b.gpu.slab.ptrs();
+        const size_t tk = clk->begin("k_count");
+        if (windowed_w(W) && knobs.count_window) {
+            const unsigned g = unsigned(std::min<uint64_t>((b.E + 4 * kC2Range - 1) / (4 * kC2Range), 1u << 16));
+            with_window_width(W, [&](auto w) {
+                hipLaunchKernelGGL(k_count2<decltype(w)::value>, dim3(g), dim3(kBlock), 0, s, uint32_t(b.E), sp.cid,
+                                   b.gpu.d_cls.as<DClass>(), sp.mem, sp.lohi, sp.pos, sp.mask, member_lo(b), member_hi(b),
+                                   cnt.as<uint32_t>(), d_tests);
+            });
+        } else {
+            const uint32_t cchunk = knobs.count_chunk;
+            with_width(W, [&](auto w) {
+                hipLaunchKernelGGL(k_count<decltype(w)::value>, dim3(unsigned((b.E + cchunk - 1) / cchunk)), dim3(kBlock),
+                                   0, s, uint32_t(b.E), sp.cid, b.gpu.d_cls.as<DClass>(), sp.mem, sp.lohi, sp.pos, sp.mask,
+                                   member_lo(b), member_hi(b), cchunk, cnt.as<uint32_t>(), d_tests, uint32_t(W));
+            });
+        }
+        FSM_LAUNCHED("k_count", s);
+        clk->end(tk, int64_t(b.E * entry_bytes() + b.n_cnt * 4), int64_t(b.E * survey_entry_bytes()));
+        return CountPath::kAtomic;
+    }
+
+    // The frequent candidates of the counted batch as records in (row, slot) order.
+    Records extract(Batch& b, CountPath path, const DevBuf& cnt) {
+        std::vector<FreqRec>& recs = recs_s;
+        if (path == CountPath::kRootF2)  // (root_f2 ordered them: on the host with rec_off_s, or on the device)
+            return Records{recs.data(), recs.size(), false, !b.dev_order, b.dev_order};
+        if (path == CountPath::kSparse) {
+            order_recs(recs, uint32_t(rows_s.size()), &rec_off_s);
+            return Records{recs.data(), recs.size(), false, true, false};
+        }
+        const auto [rlo, rhi] = row_slice(b);
+        DevBuf d_rows;
+        upload_staged(1, d_rows, rows_s.data() + rlo, size_t(rhi - rlo) * sizeof(DRow));
+        // large batches: ordered extraction (the host ordering and the mapped-memory reads of
+        // millions of records cost more than the extra sync)
+        if (rhi - rlo > kFreqOnePassRows) return extract_in_order(b, cnt, d_rows, rlo, rhi);
+        // the atomic count zeroed a record counter with its counters
+        uint32_t* d_nz = path == CountPath::kAtomic ? cnt.as<uint32_t>() + b.n_cnt : nullptr;
+        return extract_one_pass(b, cnt, d_nz, d_rows, rlo, rhi);
+    }
+    // bytes the extraction kernels read: the counter rows of the slice
+    int64_t freq_bytes(const Batch& b, uint32_t nrows) const {
+        return int64_t(uint64_t(nrows) * (b.n_cnt / std::max<uint64_t>(rows_s.size(), 1)) * 4);
+    }
+    // two passes (k_freq_count, scan, k_freq_write): records in row order straight into mapped
+    // pinned host memory, read there after the sync
+    Records extract_in_order(Batch& b, const DevBuf& cnt, const DevBuf& d_rows, uint32_t rlo, uint32_t rhi) {
+        const uint32_t nrows = rhi - rlo;
+        const unsigned grid = unsigned((uint64_t(nrows) * 64 + kBlock - 1) / kBlock);
+        DevBuf rowcnt((size_t(nrows) + 1) * 4), rowoff((size_t(nrows) + 1) * 8);
+        size_t tk = clk->begin("k_freq_count");
+        hipLaunchKernelGGL(k_freq_count, dim3(grid), dim3(kBlock), 0, s, d_rows.as<DRow>(), nrows,
+                           b.gpu.d_cls.as<DClass>(), cnt.as<uint32_t>(), minsup, rowcnt.as<uint32_t>());
+        FSM_LAUNCHED("k_freq_count", s);
+        clk->end(tk, freq_bytes(b, nrows));
+        scan_exclusive(rowcnt.as<uint32_t>(), rowoff.as<uint64_t>(), nrows, s);
+        FSM_HIP(hipMemcpyAsync(&pend[1], rowoff.as<uint64_t>() + nrows, 8, hipMemcpyDeviceToHost, s));
+        sync();
+        const uint64_t nf = pend[1];
+        if (!nf) return Records{};
+        PinnedBuf* pb = ctx->pinned_big(nf * sizeof(FreqRec));
+        // unsharded: the kid table [koff | kslot | kcid] is built here, in HBM
+        const bool dk = !comm && !knobs.kids_host;
+        const size_t nko = size_t(b.cbase_total) + 1;
+        uint32_t *kslot = nullptr, *kcid = nullptr;
+        if (dk) {
+            b.gpu.kid_tab.alloc((nko + 2 * size_t(nf)) * 4);
+            kslot = b.gpu.kid_tab.as<uint32_t>() + nko;
+            kcid = kslot + nf;
+        }
+        tk = clk->begin("k_freq_write");
+        hipLaunchKernelGGL(k_freq_write, dim3(grid), dim3(kBlock), 0, s, d_rows.as<DRow>(), nrows,
+                           b.gpu.d_cls.as<DClass>(), cnt.as<uint32_t>(), minsup, rowoff.as<uint64_t>(), rlo,
+                           static_cast<FreqRec*>(pb->dev), kslot, kcid);
+        FSM_LAUNCHED("k_freq_write", s);
+        if (dk) {
+            hipLaunchKernelGGL(k_kid_off, dim3(unsigned((nrows + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
+                               d_rows.as<DRow>(), nrows, b.gpu.d_cls.as<DClass>(), rowoff.as<uint64_t>(), uint32_t(nko),
+                               b.gpu.kid_tab.as<uint32_t>());
+            FSM_LAUNCHED("k_kid_off", s);
+        }
+        clk->end(tk, freq_bytes(b, nrows) + int64_t(nf * sizeof(FreqRec)));
+        sync();
+        return Records{static_cast<const FreqRec*>(pb->host), nf, dk, false, false};
+    }
+    // one pass (k_freq_recs): unordered records at block cursors in mapped pinned host memory,
+    // one stream sync per batch; then ordered on the device (order_device) or on the host
+    Records extract_one_pass(Batch& b, const DevBuf& cnt, uint32_t* d_nz, const DevBuf& d_rows, uint32_t rlo,
+                             uint32_t rhi) {
+        const uint32_t nrows = rhi - rlo;
+        const unsigned grid = unsigned((uint64_t(nrows) * 64 + kBlock - 1) / kBlock);
+        std::vector<FreqRec>& recs = recs_s;
+        DevBuf d_n;
+        uint32_t* dn = d_nz;  // zeroed with the counters (a retry or the keyed count: its own)
+        // the last emit's block has a zeroed counter for this count: both come back in one copy
+        const bool ride = pend_check && emit_blk && !emit_copied;
+        if (ride) dn = reinterpret_cast<uint32_t*>(emit_blk + 16);
+        PinnedBuf* pb = nullptr;
+        uint32_t nf = 0;
+        if (nrows)
+            nf = extract_capped(
+                uint32_t(std::min<uint64_t>(std::max<uint64_t>(uint64_t(nrows) * 4, 4096), b.n_cnt)),
+                "SPADE: frequent candidate buffer overflow", [&](uint32_t cap, bool retry) {
+                    pb = ctx->pinned_big(size_t(std::max<uint32_t>(cap, 1)) * sizeof(FreqRec));
+                    if (retry || dn == nullptr) {
+                        if (d_n.p == nullptr) d_n.alloc(4);
+                        dn = d_n.as<uint32_t>();
+                        FSM_HIP(hipMemsetAsync(dn, 0, 4, s));
+                    }
+                    const size_t tk = clk->begin("k_freq_recs");
+                    hipLaunchKernelGGL(k_freq_recs, dim3(grid), dim3(kBlock), 0, s, d_rows.as<DRow>(), nrows,
+                                       b.gpu.d_cls.as<DClass>(), cnt.as<uint32_t>(), minsup, rlo,
+                                       static_cast<FreqRec*>(pb->dev), cap, dn);
+                    FSM_LAUNCHED("k_freq_recs", s);
+                    clk->end(tk, freq_bytes(b, nrows));
+                    if (ride && !retry) {
+                        FSM_HIP(hipMemcpyAsync(&pend[8], emit_blk, 24, hipMemcpyDeviceToHost, s));
+                        emit_copied = true;
+                        sync();
+                        return uint32_t(pend[10] & 0xFFFFFFFFu);
+                    }
+                    FSM_HIP(hipMemcpyAsync(&pend[1], dn, 4, hipMemcpyDeviceToHost, s));
+                    sync();
+                    return uint32_t(pend[1] & 0xFFFFFFFFu);
+                });
+        // unsharded, one emit group: ordered on the device, the children deferred to emit()
+        if (nf && !comm && !knobs.kids_host) {
+            uint32_t dmax = 0;
+            for (const ClassMeta& m : b.cls) dmax = std::max(dmax, m.D);
+            if (order_device(b, pb, nf, nrows, RkRows{d_rows.as<DRow>(), b.gpu.d_cls.as<DClass>(), 0u}, dmax,
+                             size_t(b.cbase_total) + 1)) {
+                recs.clear();
+                return Records{nullptr, 0, false, false, true};
             }
         }
-        lap(13, tl2);
-        b.kid_tab.alloc(std::max<size_t>(kbytes, 4));
-        ctx->stage_copy(2, b.kid_tab.p, kbytes);
-        lap(11, tl2);
-        b.kid_off = b.kid_tab.as<uint32_t>();
-        b.kid_slot = b.kid_off + nko;
-        b.kid_cid = b.kid_slot + nfreq;
-        if (pre_co) b.child_of_pre = b.kid_cid + nfreq;
-        if (defer) {  // emit() builds the children after launching its kernels
-            hp[1] += now_ms() - th;
-            return;
+        if (nf) recs.assign(static_cast<const FreqRec*>(pb->host), static_cast<const FreqRec*>(pb->host) + nf);
+        order_recs(recs, rhi, &rec_off_s);
+        return Records{recs.data(), recs.size(), false, rhi == rows_s.size(), false};
+    }
+
+    // Sharded root: every rank gets every rank's frequent pairs, in row order (slices ascend
+    // with the rank).  The gather is the collective every rank passes before its first claim.
+    Records gather_sharded(Batch& b, const Records& own) {
+        const uint64_t n = agr.code ? 0 : own.n;
+        std::vector<uint8_t> mine(n * sizeof(FreqRec));
+        if (n) std::memcpy(mine.data(), own.R, mine.size());
+        std::vector<size_t> sizes;
+        // the claim counter of this mine's first-level classes is reset before this gather;
+        // the same all-reduce carries the failure agreement and, at the first sharded mine,
+        // whether every rank has the shared counters
+        b.claim.key = comm->next_key();
+        comm->reset_counter(b.claim.key);
+        uint32_t ex = comm->has_fetch_add() && knobs.claims ? 1u : 0u;
+        const std::vector<uint8_t> all = comm->gather_blobs(mine, sizes, s, &agr, &ex, 1);
+        if (comm->claim_mode < 0) comm->claim_mode = ex == uint32_t(comm->nranks()) ? 1 : 0;
+        std::vector<FreqRec>& recs = recs_s;
+        recs.resize(all.size() / sizeof(FreqRec));
+        if (!recs.empty()) std::memcpy(recs.data(), all.data(), all.size());
+        // the unordered-pair F2 gives a rank records of rows above its slice: (row, slot)
+        // order and the child ids over the whole set.  Every rank orders them, whatever its
+        // own F2 layout (a rank with an empty slice runs the ordered one): the ranks must
+        // derive identical children, or their collective sequences part
+        order_recs(recs, uint32_t(rows_s.size()), &rec_off_s);
+        return Records{recs.data(), recs.size(), false, true, false};
+    }
+
+    // The member slots cbase + mi that open a child class, numbered in record order into co
+    // (the child_of table of a deferred emit: its children are numbered the same way).
+    void number_child_slots(const Batch& b, const FreqRec* R, uint64_t n, const RawVec<DRow>& rows, uint32_t* co) const {
+        uint32_t k = 0;
+        for_row_groups(R, n, 0, n, [&](uint64_t q0, uint64_t q1) {
+            if (!opens_class(R, q0, q1)) return;
+            const DRow pr = rows[R[q0].row];
+            co[b.cls[pr.cls].cbase + pr.mi] = k++;
+        });
+    }
+
+    // The kid table of the batch, the frequent children of every member as a CSR over the
+    // member slots cbase + mi: one table, one H2D copy [koff: cbase_total + 1 | kslot: n |
+    // kcid: n | child_of: cbase_total, when a deferred emit takes it from the host].
+    void build_kid_table(Batch& b, const Records& recs, bool defer) {
+        const FreqRec* R = recs.R;
+        const uint64_t nfreq = recs.n;
+        const RawVec<DRow>& rows = rows_s;
+        const size_t nko = size_t(b.cbase_total) + 1;
+        b.defer.child_of = nullptr;
+        double tl = now_ms();
+        const bool pre_co = !recs.kids_on_device && defer && !child_of_device(b.cbase_total);
+        if (!recs.kids_on_device) {
+            const size_t nco = pre_co ? size_t(b.cbase_total) : 0;
+            // the table is filled straight into the pinned staging slot it is DMA'd from
+            const size_t kbytes = (nko + 2 * size_t(nfreq) + nco) * 4;
+            uint32_t* koff = static_cast<uint32_t*>(ctx->stage_host(2, kbytes));
+            uint32_t* kslot = koff + nko;
+            uint32_t* kcid = kslot + nfreq;
+            lap(kLapKidStage, tl);
+            // records are in (row, slot) order, and a row's member slot cbase + mi ascends
+            // with the row: koff[x] = records of slots < x
+            const int64_t nthk = nfreq >= knobs.host_par_min ? host_threads() : 1;
+            if (recs.row_offsets && rec_off_s.size() == rows.size() + 1) {
+                // from the row offsets of the ordering: slots (s(r-1), s(r)] take off[r]
+                uint64_t x = 0;
+                for (size_t r = 0; r < rows.size(); ++r) {
+                    const uint64_t sr = uint64_t(b.cls[rows[r].cls].cbase) + rows[r].mi;
+                    const uint32_t o = rec_off_s[r];
+                    for (; x <= sr && x < nko; ++x) koff[x] = o;
+                }
+                for (; x < nko; ++x) koff[x] = uint32_t(nfreq);
+            } else {  // (records ordered on the device: a merge, threads split x)
+                auto slot_of = [&](uint64_t q) { return uint64_t(b.cls[rows[R[q].row].cls].cbase) + rows[R[q].row].mi; };
+                par_slices(nthk, int64_t(nko), [&](int64_t, int64_t x0, int64_t x1) {
+                    uint64_t lo = 0, hi = nfreq;  // first record with slot >= x0
+                    while (lo < hi) {
+                        const uint64_t mid = (lo + hi) / 2;
+                        if (slot_of(mid) < uint64_t(x0)) lo = mid + 1; else hi = mid;
+                    }
+                    uint64_t q = lo;
+                    for (int64_t x = x0; x < x1; ++x) {
+                        while (q < nfreq && slot_of(q) < uint64_t(x)) ++q;
+                        koff[x] = uint32_t(q);
+                    }
+                });
+            }
+            par_slices(nthk, int64_t(nfreq), [&](int64_t, int64_t q0, int64_t q1) {
+                for (int64_t q = q0; q < q1; ++q) {  // recs are ordered by (row, slot) = CSR order
+                    kslot[q] = R[q].slot;
+                    kcid[q] = R[q].cid;
+                }
+            });
+            lap(kLapKidFill, tl);
+            if (pre_co) {
+                std::fill(kcid + nfreq, kcid + nfreq + nco, kNone);
+                number_child_slots(b, R, nfreq, rows, kcid + nfreq);
+            }
+            lap(kLapChildOf, tl);
+            b.gpu.kid_tab.alloc(std::max<size_t>(kbytes, 4));
+            ctx->stage_copy(2, b.gpu.kid_tab.p, kbytes);
+            lap(kLapKidCopy, tl);
         }
+        b.gpu.kid_off = b.gpu.kid_tab.as<uint32_t>();
+        b.gpu.kid_slot = b.gpu.kid_off + nko;
+        b.gpu.kid_cid = b.gpu.kid_slot + nfreq;
+        if (pre_co) b.defer.child_of = b.gpu.kid_cid + nfreq;
+    }
+
+    // The one-group test of pack_groups, from the records alone (before the children exist):
+    // unsharded, no claims, every kept child in one group.  Then the batch records what
+    // emit() needs (the group, the child entry total) and defers the children to it.
+    bool defer_ok(Batch& b, const Records& recs) {
+        double tl = now_ms();
+        const FreqRec* R = recs.R;
+        const uint64_t nfreq = recs.n;
+        b.defer.on = false;
+        if (comm || b.claim.key >= 0 || nfreq == 0 || !knobs.emit_defer) return false;
+        // the rows' sums over host-thread slices of the records (SIGN-shaped batches hold
+        // millions of records)
+        const int64_t nthr = nfreq >= knobs.host_par_min ? host_threads() : 1;
+        std::vector<uint64_t> sl(size_t(nthr) * 3, 0);  // need, ent, nkept per slice
+        const size_t eb = entry_bytes();
+        par_slices(nthr, int64_t(nfreq), [&](int64_t t, int64_t a, int64_t z) {
+            uint64_t need = 0, ent = 0, nkept = 0;
+            for_row_groups(R, nfreq, uint64_t(a), uint64_t(z), [&](uint64_t q0, uint64_t q1) {
+                if (!opens_class(R, q0, q1)) return;
+                uint64_t sup = 0;
+                for (uint64_t q = q0; q < q1; ++q) sup += R[q].sup;
+                const uint64_t D = 2ull * child_ranks(R, q0, q1);
+                need += sup * eb + D * D * 4;
+                ent += sup;
+                ++nkept;
+            });
+            sl[size_t(t) * 3] = need;
+            sl[size_t(t) * 3 + 1] = ent;
+            sl[size_t(t) * 3 + 2] = nkept;
+        });
+        uint64_t need = 0, ent = 0, nkept = 0;
+        for (int64_t t = 0; t < nthr; ++t) {
+            need += sl[size_t(t) * 3];
+            ent += sl[size_t(t) * 3 + 1];
+            nkept += sl[size_t(t) * 3 + 2];
         }
-        hp[1] += now_ms() - th;
-        th = now_ms();
-        // emit() builds the children after launching its kernels (one group, unsharded)
-        if (!defer_checked && defer_ok(b, R, nfreq, rows)) {
-            hp[2] += now_ms() - th;
-            return;
-        }
-        make_children(b, R, nfreq, rows);
-        if (shard) {
+        lap(kLapDeferOk, tl);
+        if (need > budget || ent > kMaxGroupEntries || nkept == 0) return false;
+        b.children.clear();
+        b.groups.assign(1, {size_t(0), size_t(nkept)});
+        b.next_group = 0;
+        b.defer.on = true;
+        b.defer.R = R;
+        b.defer.n = nfreq;
+        b.defer.total = ent;
+        b.defer.rows = &rows_s;
+        return true;
+    }
+
+    // Sharded mining: which of the children this rank mines.
+    void plan_first_level(Batch& b) {
+        if (comm && b.root) {
             // first-level classes: largest-first by estimated id-list volume (the
             // class's entries), same plan on every rank; keep this rank's share.
-            // A class heavier than split_frac() of a rank's fair share is split instead:
+            // A class heavier than FSM_SPLIT_FRAC of a rank's fair share is split instead:
             // every rank counts it, and its sub-classes are planned over the ranks.
             n_shared = nodes.size();
             const size_t nc = b.children.size();
@@ -3839,7 +3991,7 @@ struct Miner {
             std::vector<size_t> idx;
             std::vector<uint8_t> heavy(nc, 0);
             for (size_t k = 0; k < nc; ++k) {
-                heavy[k] = nc > 1 && double(b.children[k].cap) * double(N) > split_frac() * double(tot);
+                heavy[k] = nc > 1 && double(b.children[k].cap) * double(N) > knobs.split_frac * double(tot);
                 if (!heavy[k]) {
                     vol.push_back(b.children[k].cap);
                     idx.push_back(k);
@@ -3855,7 +4007,7 @@ struct Miner {
             // about 5,000) the largest-first plan is within a few percent, and every claim costs
             // an emit pass over all the DB rows (0.3 ms at D1M), so the static plan runs (one
             // pass per rank).  FSM_SPADE_CLAIMS=1 forces claims, =0 the static plan.
-            const bool claims_pay = claims_forced() || nc < kClaimClassesPerRank * uint64_t(comm->nranks());
+            const bool claims_pay = knobs.claims_forced || nc < kClaimClassesPerRank * uint64_t(comm->nranks());
             if (comm->claim_mode == 1 && claims_pay) {
                 // work stealing: heavy classes first (every rank), then the rest largest first;
                 // the groups after the shared ones are claimed from the shared counter
@@ -3868,7 +4020,7 @@ struct Miner {
                 const size_t h = all.size();
                 for (size_t k : ord) all.push_back(std::move(b.children[k]));
                 b.children = std::move(all);
-                b.nshared_children = h;
+                b.claim.nshared = h;
             } else {
                 std::vector<int32_t> owner(vol.size());
                 shard_plan(vol.data(), int64_t(vol.size()), comm->nranks(), owner.data());
@@ -3878,11 +4030,11 @@ struct Miner {
                 for (size_t k = 0; k < nc; ++k)
                     if (heavy[k] || keep[k]) kept.push_back(std::move(b.children[k]));
                 b.children = std::move(kept);
-                b.claim_key = -1;
+                b.claim.key = -1;
             }
             if (ctx->opts.verbose)
                 std::fprintf(stderr, "[fsm] rank %d: %zu first-level classes, %zu %s, %zu heavy (split)\n",
-                             comm->rank(), nc, b.children.size(), b.claim_key >= 0 ? "claimable" : "kept", nheavy);
+                             comm->rank(), nc, b.children.size(), b.claim.key >= 0 ? "claimable" : "kept", nheavy);
         } else if (comm) {
             // sub-classes of a split class: LPT over that class's sub-classes alone
             // (the same on every rank whatever the batching), this rank keeps its share
@@ -3906,29 +4058,22 @@ struct Miner {
             for (ChildInfo& c : kept) c.split = false;
             b.children = std::move(kept);
         }
-        hp[2] += now_ms() - th;
-        th = now_ms();
-        if (b.claim_key >= 0) {
-            // work stealing: the shared (heavy) groups now, the claimed ones as they come
-            b.groups.clear();
-            b.next_group = 0;
-            append_groups(b, 0, b.nshared_children);
-            const size_t h = b.nshared_children, n = b.children.size() - h;
-            b.claim_pre.assign(n + 1, 0);
-            for (size_t k = 0; k < n; ++k) b.claim_pre[k + 1] = b.claim_pre[k] + b.children[h + k].cap;
-            hp[3] += now_ms() - th;
-            return;
-        }
-        // groups of children that fit the frontier budget
+    }
+
+    // the children in emit groups that fit the frontier budget
+    void pack_groups(Batch& b) {
         b.groups.clear();
         b.next_group = 0;
-        size_t gs = 0;
-        uint64_t acc = 0;
-        const uint64_t max_ent = uint64_t(1) << 31;
-        uint64_t acc_ent = 0;
+        if (b.claim.key >= 0) {
+            // work stealing: the shared (heavy) groups now, the claimed ones as they come
+            append_groups(b, 0, b.claim.nshared);
+            const size_t h = b.claim.nshared, n = b.children.size() - h;
+            b.claim.pre.assign(n + 1, 0);
+            for (size_t k = 0; k < n; ++k) b.claim.pre[k + 1] = b.claim.pre[k] + b.children[h + k].cap;
+            return;
+        }
         const int64_t nch = int64_t(b.children.size());
-        bool one = false;  // many children: the common case (all fit one group) from threaded sums
-        if (nch >= (int64_t(1) << 16)) {
+        if (nch >= (int64_t(1) << 16)) {  // many children: the common case (all fit one group) from threaded sums
             const int64_t nthr = host_threads();
             std::vector<uint64_t> tn(size_t(nthr), 0), te(size_t(nthr), 0);
             par_slices(nthr, nch, [&](int64_t t, int64_t k0, int64_t k1) {
@@ -3941,158 +4086,25 @@ struct Miner {
                 tn[size_t(t)] = n;
                 te[size_t(t)] = e;
             });
-            uint64_t n = 0, e = 0;
-            for (int64_t t = 0; t < nthr; ++t) {
-                n += tn[size_t(t)];
-                e += te[size_t(t)];
+            const uint64_t n = std::accumulate(tn.begin(), tn.end(), uint64_t(0));
+            const uint64_t e = std::accumulate(te.begin(), te.end(), uint64_t(0));
+            if (n <= budget && e <= kMaxGroupEntries) {
+                b.groups.push_back({0, b.children.size()});
+                return;
             }
-            one = n <= budget && e <= max_ent;
         }
-        if (one) gs = b.children.size();
-        for (size_t k = one ? b.children.size() : 0; k < b.children.size(); ++k) {
-            const uint64_t need = b.children[k].cap * entry_bytes() + uint64_t(b.children[k].D) * b.children[k].D * 4;
-            if (k > gs && (acc + need > budget || acc_ent + b.children[k].cap > max_ent)) {
-                b.groups.push_back({gs, k});
-                gs = k;
-                acc = 0;
-                acc_ent = 0;
-            }
-            acc += need;
-            acc_ent += b.children[k].cap;
-        }
-        if (one) b.groups.push_back({0, b.children.size()});
-        else if (gs < b.children.size()) b.groups.push_back({gs, b.children.size()});
-        hp[3] += now_ms() - th;
-        if (ctx->opts.verbose)
-            std::fprintf(stderr, "[fsm] batch: classes=%zu entries=%llu freq=%llu children=%zu groups=%zu\n",
-                         b.cls.size(), (unsigned long long)tot_ent, (unsigned long long)nfreq,
-                         b.children.size(), b.groups.size());
+        append_groups(b, 0, b.children.size());
     }
-
-    // the children of a counted batch (new pattern nodes, the next batch's class records and
-    // member tables) in deterministic (row, slot) order
-    void make_children(Batch& b, const FreqRec* R, uint64_t nfreq, const RawVec<DRow>& rows) {
-        fsm_stats& st = ctx->stats;
-        b.children.clear();
-        b.child_rank_item.clear();
-        b.child_node_of.clear();
-        b.children.reserve(nfreq);
-        b.child_rank_item.reserve(nfreq + 16);
-        b.child_node_of.reserve(2 * nfreq + 16);
-        if (!comm && nfreq >= par_min()) {
-            children_parallel(b, R, nfreq, rows);
-        } else
-        for (size_t q = 0; q < nfreq;) {
-            const uint32_t row = R[q].row;
-            const DRow pr = rows[row];
-            const ClassMeta& pm = b.cls[pr.cls];
-            size_t q2 = q;
-            uint32_t maxcid = 0;
-            while (q2 < nfreq && R[q2].row == row) { maxcid = std::max(maxcid, R[q2].cid); ++q2; }
-            ChildInfo ch;
-            ch.pcls = pr.cls;
-            ch.pmi = pr.mi;
-            const uint32_t R2 = (maxcid >> 1) + 1;
-            ch.D = 2 * R2;
-            ch.ri_off = b.child_rank_item.size();
-            ch.no_off = b.child_node_of.size();
-            b.child_rank_item.resize(ch.ri_off + R2, 0);
-            b.child_node_of.resize(ch.no_off + ch.D, -1);
-            const int32_t parent = b.node_of[pm.no_off + pr.mi];
-            const uint32_t pls = nodes[size_t(parent)].len_sets;
-            ch.psup = nodes[size_t(parent)].support;
-            if ((pls >> 16) >= 0xFFFFu) throw Error(FSM_ELIMIT, "SPADE: a pattern exceeds 65534 items");
-            const bool dup = comm && pm.split && comm->rank() != 0;  // a split class's nodes: rank 0 outputs them
-            uint32_t last_type = 0;
-            for (size_t k = q; k < q2; ++k) {
-                const FreqRec& fr = R[k];
-                const uint32_t item = b.rank_item[pm.ri_off + (fr.slot >> 1)];
-                const int32_t node = int32_t(nodes.size());
-                nodes.push_back(PNode{parent, item, fr.slot & 1u, fr.sup, pls + (1u << 16) + ((fr.slot & 1u) == kSeq)});
-                if (dup) {
-                    node_dup.resize(nodes.size(), 0);
-                    node_dup[size_t(node)] = 1;
-                }
-                b.child_rank_item[ch.ri_off + (fr.cid >> 1)] = item;
-                b.child_node_of[ch.no_off + fr.cid] = node;
-                ch.cap += fr.sup;
-                if ((fr.slot & 1u) == kSeq) { ++ch.nS; ch.sS += fr.sup; } else { ++ch.nI; ch.sI += fr.sup; }
-                if (!dup) st.bytes_join_equiv += int64_t(12ull * fr.sup);
-                last_type = fr.slot & 1u;
-            }
-            const size_t nch = q2 - q;
-            if (!(nch == 1 && last_type == kItm)) b.children.push_back(std::move(ch));
-            q = q2;
-        }
-    }
-
-    // The one-group test of count_and_freq's group split, from the records alone (before the
-    // children exist): unsharded, no claims, every kept child in one group.  Then the batch
-    // records what emit() needs (the group, the child entry total) and defers the children.
-    bool defer_ok(Batch& b, const FreqRec* R, uint64_t nfreq, const RawVec<DRow>& rows) {
-        b.defer_children = false;
-        if (comm || b.claim_key >= 0 || nfreq == 0 || defer_env() == 0) return false;
-        // the rows' sums over host-thread slices of the records (a slice takes the rows that start
-        // in it, whole; SIGN-shaped batches hold millions of records)
-        const int64_t nthr = nfreq >= par_min() ? host_threads() : 1;
-        std::vector<uint64_t> sl(size_t(nthr) * 3, 0);  // need, ent, nkept per slice
-        const size_t eb = entry_bytes();
-        par_slices(nthr, int64_t(nfreq), [&](int64_t t, int64_t q0, int64_t q1) {
-            uint64_t q = uint64_t(q0), need = 0, ent = 0, nkept = 0;
-            while (q0 > 0 && q < uint64_t(q1) && R[q].row == R[q - 1].row) ++q;  // (a row that started before)
-            while (q < uint64_t(q1)) {
-                const uint32_t row = R[q].row;
-                uint64_t q2 = q, sup = 0;
-                uint32_t maxcid = 0;
-                while (q2 < nfreq && R[q2].row == row) {
-                    maxcid = std::max(maxcid, R[q2].cid);
-                    sup += R[q2].sup;
-                    ++q2;
-                }
-                if (!(q2 - q == 1 && (R[q].slot & 1u) == kItm)) {
-                    const uint64_t D = 2ull * ((maxcid >> 1) + 1);
-                    need += sup * eb + D * D * 4;
-                    ent += sup;
-                    ++nkept;
-                }
-                q = q2;
-            }
-            sl[size_t(t) * 3] = need;
-            sl[size_t(t) * 3 + 1] = ent;
-            sl[size_t(t) * 3 + 2] = nkept;
-        });
-        uint64_t need = 0, ent = 0, nkept = 0;
-        for (int64_t t = 0; t < nthr; ++t) {
-            need += sl[size_t(t) * 3];
-            ent += sl[size_t(t) * 3 + 1];
-            nkept += sl[size_t(t) * 3 + 2];
-        }
-        if (need > budget || ent > (uint64_t(1) << 31) || nkept == 0) return false;
-        b.children.clear();
-        b.groups.assign(1, {size_t(0), size_t(nkept)});
-        b.next_group = 0;
-        b.defer_children = true;
-        b.defer_R = R;
-        b.defer_n = nfreq;
-        b.defer_total = ent;
-        b.defer_rows = &rows;
-        return true;
-    }
-    // FSM_EMIT_DEFER=0: children built before the emit launch (A/B)
-    static int defer_env() {  // (read per batch: the tests switch it within one process)
-        const char* e = std::getenv("FSM_EMIT_DEFER");
-        return e && e[0] == '0' ? 0 : 1;
-    }
+    static constexpr uint64_t kMaxGroupEntries = uint64_t(1) << 31;  // entries of one emit group (one slab)
 
     // groups of children [a, z) that fit the frontier budget, appended to b.groups
     void append_groups(Batch& b, size_t a, size_t z) {
-        const uint64_t max_ent = uint64_t(1) << 31;
         size_t gs = a;
         uint64_t acc = 0, acc_ent = 0;
         for (size_t k = a; k < z; ++k) {
             const ChildInfo& c = b.children[k];
             const uint64_t need = c.cap * entry_bytes() + uint64_t(c.D) * c.D * 4;
-            if (k > gs && (acc + need > budget || acc_ent + c.cap > max_ent)) {
+            if (k > gs && (acc + need > budget || acc_ent + c.cap > kMaxGroupEntries)) {
                 b.groups.push_back({gs, k});
                 gs = k;
                 acc = acc_ent = 0;
@@ -4102,56 +4114,42 @@ struct Miner {
         }
         if (gs < z) b.groups.push_back({gs, z});
     }
-    // FSM_SPADE_CLAIMS=0: the sharded lattice splits the first-level classes by the static
-    // plan even when the shared counters exist (tests, A/B)
-    static bool claims_env() {
-        const char* v = std::getenv("FSM_SPADE_CLAIMS");
-        return !(v && v[0] == '0');
-    }
-    static bool claims_forced() {
-        const char* v = std::getenv("FSM_SPADE_CLAIMS");
-        return v && v[0] == '1';
-    }
     // below this many first-level classes per rank the sharded lattice claims its classes
     static constexpr uint64_t kClaimClassesPerRank = 64;
-    // a rank's first claim takes this fraction of its fair share of the claimable volume
-    // (FSM_CLAIM_FIRST); later claims half of the remaining volume's fair share, at least
-    // 1/8 of the fair share (guided self-scheduling: few claims, each an emit pass over the DB).
-    // A value >= the rank count makes a first claim take every class (the regression test of
-    // a first claim that covers the whole class list)
-    static double claim_first() {
-        const char* v = std::getenv("FSM_CLAIM_FIRST");
-        return v ? std::clamp(std::atof(v), 0.01, 64.0) : 0.7;
-    }
     // Claim the next range of first-level classes from the shared counter and append its
     // groups; false when every class is claimed.  Two atomics: a read of the counter to
     // size the claim by the remaining volume, then the add that takes it.
+    // A rank's first claim takes knobs.claim_first of its fair share of the claimable volume;
+    // later claims half of the remaining volume's fair share, at least 1/8 of the fair share
+    // (guided self-scheduling: few claims, each an emit pass over the DB).  A claim_first >=
+    // the rank count makes a first claim take every class (the regression test of a first
+    // claim that covers the whole class list).
     bool claim_more(Batch& b) {
-        if (b.claim_key < 0 || b.claims_done) return false;
-        const size_t h = b.nshared_children, n = b.children.size() - h;
-        const int64_t pos0 = comm->fetch_add(b.claim_key, 0);
+        if (b.claim.key < 0 || b.claim.done) return false;
+        const size_t h = b.claim.nshared, n = b.children.size() - h;
+        const int64_t pos0 = comm->fetch_add(b.claim.key, 0);
         if (pos0 < 0) throw Error(FSM_ECOMM, "SPADE: work-stealing counter failed");
         if (uint64_t(pos0) >= n) {
-            b.claims_done = true;
+            b.claim.done = true;
             return false;
         }
-        const uint64_t N = uint64_t(comm->nranks()), tot = b.claim_pre[n], rem = tot - b.claim_pre[size_t(pos0)];
-        uint64_t target = b.claims_made == 0 ? uint64_t(claim_first() * double(tot) / double(N))
+        const uint64_t N = uint64_t(comm->nranks()), tot = b.claim.pre[n], rem = tot - b.claim.pre[size_t(pos0)];
+        uint64_t target = b.claim.made == 0 ? uint64_t(knobs.claim_first * double(tot) / double(N))
                                               : std::max(rem / (2 * N), tot / (8 * N));
         target = std::max<uint64_t>(target, 1);
         // the fewest classes from pos0 whose volume reaches the target
-        const uint64_t want = b.claim_pre[size_t(pos0)] + target;
-        size_t m = size_t(std::lower_bound(b.claim_pre.begin() + pos0 + 1, b.claim_pre.end(), want) -
-                          b.claim_pre.begin()) - size_t(pos0);
+        const uint64_t want = b.claim.pre[size_t(pos0)] + target;
+        size_t m = size_t(std::lower_bound(b.claim.pre.begin() + pos0 + 1, b.claim.pre.end(), want) -
+                          b.claim.pre.begin()) - size_t(pos0);
         m = std::clamp<size_t>(m, 1, n - size_t(pos0));
-        const int64_t old = comm->fetch_add(b.claim_key, int64_t(m));
+        const int64_t old = comm->fetch_add(b.claim.key, int64_t(m));
         if (old < 0) throw Error(FSM_ECOMM, "SPADE: work-stealing counter failed");
         if (uint64_t(old) >= n) {
-            b.claims_done = true;
+            b.claim.done = true;
             return false;
         }
         append_groups(b, h + size_t(old), h + std::min<size_t>(size_t(old) + m, n));
-        ++b.claims_made;
+        ++b.claim.made;
         ctx->stats.rank_claims += 1;
         return true;
     }
@@ -4166,25 +4164,13 @@ struct Miner {
         // children, so the host builds the table
         const bool dev_child_of = comm == nullptr && !b.dev_order && child_of_device(b.cbase_total);
         RawVec<uint32_t>& child_of = child_of_s;
-        if (!dev_child_of && !(b.defer_children && b.child_of_pre)) child_of.assign(b.cbase_total, kNone);
+        if (!dev_child_of && !(b.defer.on && b.defer.child_of)) child_of.assign(b.cbase_total, kNone);
         uint64_t total = 0;
-        const bool deferred = b.defer_children;  // (one group; the children are built after the launch)
+        const bool deferred = b.defer.on;  // (one group; the children are built after the launch)
         if (deferred) {
-            total = b.defer_total;
-            if (!dev_child_of && !b.child_of_pre) {  // the member slots that open a class, numbered in record order
-                const FreqRec* R = b.defer_R;
-                const RawVec<DRow>& rows = *b.defer_rows;
-                uint32_t k = 0;
-                for (uint64_t q = 0; q < b.defer_n;) {
-                    uint64_t q2 = q;
-                    while (q2 < b.defer_n && R[q2].row == R[q].row) ++q2;
-                    if (!(q2 - q == 1 && (R[q].slot & 1u) == kItm)) {
-                        const DRow pr = rows[R[q].row];
-                        child_of[b.cls[pr.cls].cbase + pr.mi] = k++;
-                    }
-                    q = q2;
-                }
-            }
+            total = b.defer.total;
+            if (!dev_child_of && !b.defer.child_of)
+                number_child_slots(b, b.defer.R, b.defer.n, *b.defer.rows, child_of.data());
         }
         if (b.root && !deferred)  // the root entries this rank joins as the owner: its first-level classes' prefix supports
             for (size_t k = ga; k < gb; ++k) ctx->stats.rank_root_owned += int64_t(b.children[k].psup);
@@ -4192,7 +4178,7 @@ struct Miner {
         // the parent, released after this emit and recycled, keeps nb's old capacity)
         // (not a claiming root: it stays on the stack for its next claim, which reads its children;
         // a first claim covering every class would otherwise leave it with nb's old ones)
-        const bool whole = !deferred && ga == 0 && gb == b.children.size() && b.groups.size() == 1 && b.claim_key < 0;
+        const bool whole = !deferred && ga == 0 && gb == b.children.size() && b.groups.size() == 1 && b.claim.key < 0;
         if (deferred) {
         } else if (whole) {
             nb.cls.clear();
@@ -4234,113 +4220,91 @@ struct Miner {
         }
         if (total >= kNone) throw Error(FSM_ELIMIT, "SPADE: class batch exceeds 2^32 entries");
         const double th2 = now_ms();
-        hp[4] += th2 - th;
-        nb.slab.alloc(total, W);
-        hp[5] += now_ms() - th2;
+        hp[kEmitTables] += th2 - th;
+        nb.gpu.slab.alloc(total, W);
+        hp[kSlabAlloc] += now_ms() - th2;
         nb.E = total;
         DevBuf d_child_of, d_long;  // (freed into the stream-ordered pool: later launches on this stream reuse them)
         if (dev_child_of) {
             const uint32_t n = uint32_t(b.cbase_total);
             d_child_of.alloc(std::max<size_t>(n, 1) * 4);
             if (n) {
-                if (b.child_pre.p == nullptr) {  // the slot numbering, once per batch (every group reuses it)
+                if (b.gpu.child_pre.p == nullptr) {  // the slot numbering, once per batch (every group reuses it)
                     DevBuf flag(size_t(n) * 4);
-                    b.child_pre.alloc((size_t(n) + 1) * 8);
+                    b.gpu.child_pre.alloc((size_t(n) + 1) * 8);
                     const unsigned gr = unsigned(std::min<uint64_t>((n + kBlock - 1) / kBlock, 8192));
-                    hipLaunchKernelGGL(k_child_flag, dim3(gr), dim3(kBlock), 0, s, b.kid_off, b.kid_slot, n,
+                    hipLaunchKernelGGL(k_child_flag, dim3(gr), dim3(kBlock), 0, s, b.gpu.kid_off, b.gpu.kid_slot, n,
                                        flag.as<uint32_t>());
                     FSM_LAUNCHED("k_child_flag", s);
-                    scan_exclusive(flag.as<uint32_t>(), b.child_pre.as<uint64_t>(), n, s);
+                    scan_exclusive(flag.as<uint32_t>(), b.gpu.child_pre.as<uint64_t>(), n, s);
                 }
                 const unsigned gr = unsigned(std::min<uint64_t>((n + kBlock - 1) / kBlock, 8192));
-                hipLaunchKernelGGL(k_child_of, dim3(gr), dim3(kBlock), 0, s, b.kid_off, b.kid_slot,
-                                   b.child_pre.as<uint64_t>(), n, uint32_t(ga), uint32_t(gb), d_child_of.as<uint32_t>());
+                hipLaunchKernelGGL(k_child_of, dim3(gr), dim3(kBlock), 0, s, b.gpu.kid_off, b.gpu.kid_slot,
+                                   b.gpu.child_pre.as<uint64_t>(), n, uint32_t(ga), uint32_t(gb), d_child_of.as<uint32_t>());
                 FSM_LAUNCHED("k_child_of", s);
             }
-        } else if (!(deferred && b.child_of_pre)) {
+        } else if (!(deferred && b.defer.child_of)) {
             upload_staged(3, d_child_of, child_of.data(), child_of.size() * 4);
         }
         // (deferred with the host table: it came up with the kid table)
-        const uint32_t* cof = deferred && b.child_of_pre ? b.child_of_pre : d_child_of.as<uint32_t>();
+        const uint32_t* cof = deferred && b.defer.child_of ? b.defer.child_of : d_child_of.as<uint32_t>();
         ctx->stats.bytes_streamed += int64_t((total + b.E) * entry_bytes());
         if (b.E) {
             // the DB-direct root is read from the DB rows themselves (pos: the DB's row
             // positions, members through rk2, lohi from the masks)
             const bool rootdb = b.db_direct;
             const uint64_t Eg = rootdb ? uint64_t(db->E) : b.E;  // entries the kernels walk
-            SlabPtrs sp = b.slab.ptrs();
+            SlabPtrs sp = b.gpu.slab.ptrs();
             RootRef rr{nullptr, nullptr};
             if (rootdb) {
-                sp = SlabPtrs{nullptr, b.mem_db.as<uint32_t>(), nullptr, db->pos.as<uint32_t>(), db->mask.as<uint64_t>(),
+                sp = SlabPtrs{nullptr, b.f2.mem_db.as<uint32_t>(), nullptr, db->pos.as<uint32_t>(), db->mask.as<uint64_t>(),
                               nullptr};
-                rr = RootRef{db->item.as<uint32_t>(), b.rk2.as<uint32_t>()};
+                rr = RootRef{db->item.as<uint32_t>(), b.f2.rk2.as<uint32_t>()};
             }
-            SlabPtrs op = nb.slab.ptrs();
+            SlabPtrs op = nb.gpu.slab.ptrs();
             // u64 slab cursor | u32 long-run count (k_emit2) | u32 run-length flag
             // (32 bytes: the next count's record counter rides along, read back with it)
-            char* cursor = static_cast<char*>(zslot(32));
-            if (!cursor) {
-                emit_own.alloc(32);
-                FSM_HIP(hipMemsetAsync(emit_own.p, 0, 32, s));
-                cursor = emit_own.as<char>();
-            }
+            char* cursor = zeroed_slot(32, emit_own);
+            unsigned long long* cur = reinterpret_cast<unsigned long long*>(cursor);
+            uint32_t* nlong = reinterpret_cast<uint32_t*>(cursor + 8);
             op.lim = reinterpret_cast<uint32_t*>(cursor + 12);
-            const uint64_t chunk = uint64_t(kEmitBlock) * kEmitRounds;
-            const unsigned grid = unsigned(std::min<uint64_t>((Eg + chunk - 1) / chunk, emit_grid_cap()));
             const size_t tk = clk->begin("k_emit");
-            if ((W == 1 || W == 2 || W == 4 || W == 8) && emit_window()) {
+            // k_emit1 over g1 blocks: every entry in chunks (runs = nullptr), or k_emit2's long runs
+            auto emit1 = [&](auto w, auto root, unsigned g1, const uint32_t* runs, const uint32_t* nruns) {
+                hipLaunchKernelGGL((k_emit1<decltype(w)::value, decltype(root)::value>), dim3(g1), dim3(kEmitBlock), 0, s,
+                                   uint32_t(Eg), rr, sp.cid, b.gpu.d_cls.as<DClass>(), sp.mem, sp.lohi, sp.pos, sp.mask,
+                                   b.gpu.kid_off, b.gpu.kid_slot, b.gpu.kid_cid, cof, cur, op, nb.gpu.slab.cap,
+                                   knobs.emit1_cap, uint32_t(W), runs, nruns);
+            };
+            auto with_root = [&](auto&& f) {  // f(std::bool_constant<the DB-direct root>)
+                if (rootdb) f(std::true_type{});
+                else f(std::false_type{});
+            };
+            if (windowed_w(W) && knobs.emit_window) {
                 // windows of whole runs in registers; the runs of more than 64 entries go to
                 // k_emit1's run list (device-side count: no host round trip)
                 // (grid: the entries over one block's wave ranges, per kernel kind, capped)
                 d_long.alloc(std::max<uint64_t>(Eg / 65 + 1, 1) * 4);
-#define FSM_EMIT2(WW, RT)                                                                                       \
-    hipLaunchKernelGGL((k_emit2<WW, RT>), dim3(unsigned(std::min<uint64_t>(                                         \
-                           (Eg + uint64_t(e2_block<RT, WW>() / 64) * e2_range<RT, WW>() - 1) /                     \
-                           (uint64_t(e2_block<RT, WW>() / 64) * e2_range<RT, WW>()), emit_grid_cap()))),           \
-                       dim3(e2_block<RT, WW>()), 0, s, uint32_t(Eg), rr, sp.cid,                                     \
-                       b.d_cls.as<DClass>(), sp.mem, sp.lohi, sp.pos, sp.mask, b.kid_off, b.kid_slot, b.kid_cid,   \
-                       cof, reinterpret_cast<unsigned long long*>(cursor), op, nb.slab.cap, emit2_cap(),   \
-                       d_long.as<uint32_t>(), reinterpret_cast<uint32_t*>(cursor + 8));               \
-    FSM_LAUNCHED("k_emit2", s);                                                                                    \
-    hipLaunchKernelGGL((k_emit1<WW, RT>), dim3(256), dim3(kEmitBlock), 0, s, uint32_t(Eg), rr, sp.cid,              \
-                       b.d_cls.as<DClass>(), sp.mem, sp.lohi, sp.pos, sp.mask, b.kid_off, b.kid_slot, b.kid_cid,   \
-                       cof, reinterpret_cast<unsigned long long*>(cursor), op, nb.slab.cap, emit_cap(),    \
-                       uint32_t(WW), d_long.as<uint32_t>(), reinterpret_cast<const uint32_t*>(cursor + 8)); \
-    FSM_LAUNCHED("k_emit1", s);
-                switch (W * 2 + (rootdb ? 1 : 0)) {
-                    case 2: FSM_EMIT2(1, false) break;
-                    case 3: FSM_EMIT2(1, true) break;
-                    case 4: FSM_EMIT2(2, false) break;
-                    case 5: FSM_EMIT2(2, true) break;
-                    case 8: FSM_EMIT2(4, false) break;
-                    case 9: FSM_EMIT2(4, true) break;
-                    case 16: FSM_EMIT2(8, false) break;
-                    default: FSM_EMIT2(8, true) break;
-                }
-#undef FSM_EMIT2
+                with_window_width(W, [&](auto w) {
+                    with_root([&](auto root) {
+                        constexpr int WW = decltype(w)::value;
+                        constexpr bool RT = decltype(root)::value;
+                        const uint64_t per_block = uint64_t(e2_block<RT, WW>() / 64) * e2_range<RT, WW>();
+                        hipLaunchKernelGGL((k_emit2<WW, RT>),
+                                           dim3(unsigned(std::min<uint64_t>((Eg + per_block - 1) / per_block, knobs.emit_grid))),
+                                           dim3(e2_block<RT, WW>()), 0, s, uint32_t(Eg), rr, sp.cid, b.gpu.d_cls.as<DClass>(),
+                                           sp.mem, sp.lohi, sp.pos, sp.mask, b.gpu.kid_off, b.gpu.kid_slot, b.gpu.kid_cid, cof,
+                                           cur, op, nb.gpu.slab.cap, knobs.emit2_cap, d_long.as<uint32_t>(), nlong);
+                        FSM_LAUNCHED("k_emit2", s);
+                        emit1(w, root, 256u, d_long.as<uint32_t>(), nlong);
+                        FSM_LAUNCHED("k_emit1", s);
+                    });
+                });
             } else {
-#define FSM_EMIT1(WW)                                                                                               \
-    hipLaunchKernelGGL((k_emit1<WW, false>), dim3(grid), dim3(kEmitBlock), 0, s, uint32_t(Eg), rr, sp.cid,                \
-                       b.d_cls.as<DClass>(), sp.mem, sp.lohi, sp.pos, sp.mask, b.kid_off, b.kid_slot,                   \
-                       b.kid_cid, cof, reinterpret_cast<unsigned long long*>(cursor), op,  \
-                       nb.slab.cap, emit_cap(), uint32_t(W), (const uint32_t*)nullptr, (const uint32_t*)nullptr)
-#define FSM_EMIT1R(WW)                                                                                              \
-    hipLaunchKernelGGL((k_emit1<WW, true>), dim3(grid), dim3(kEmitBlock), 0, s, uint32_t(Eg), rr, sp.cid,                 \
-                       b.d_cls.as<DClass>(), sp.mem, sp.lohi, sp.pos, sp.mask, b.kid_off, b.kid_slot,                   \
-                       b.kid_cid, cof, reinterpret_cast<unsigned long long*>(cursor), op,  \
-                       nb.slab.cap, emit_cap(), uint32_t(W), (const uint32_t*)nullptr, (const uint32_t*)nullptr)
-                if (rootdb) {
-                    switch (W) {
-                        case 1: FSM_EMIT1R(1); break;
-                        case 2: FSM_EMIT1R(2); break;
-                        case 4: FSM_EMIT1R(4); break;
-                        default: FSM_EMIT1R(8); break;
-                    }
-                } else {
-                    FSM_W_DISPATCH(W, FSM_EMIT1)
-                }
-#undef FSM_EMIT1
-#undef FSM_EMIT1R
+                const uint64_t chunk = uint64_t(kEmitBlock) * kEmitRounds;
+                const unsigned grid = unsigned(std::min<uint64_t>((Eg + chunk - 1) / chunk, knobs.emit_grid));
+                if (rootdb) with_window_width(W, [&](auto w) { emit1(w, std::true_type{}, grid, nullptr, nullptr); });
+                else with_width(W, [&](auto w) { emit1(w, std::false_type{}, grid, nullptr, nullptr); });
                 FSM_LAUNCHED("k_emit", s);
             }
             // reads every parent entry once (DB-direct root: the DB entry's item, pos and mask),
@@ -4364,14 +4328,14 @@ struct Miner {
             // the children, while the emit runs: pattern nodes and the next batch's class tables,
             // moved over whole (the only group)
             const double td = now_ms();
-            b.defer_children = false;
-            if (b.dev_order) FSM_HIP(hipEventSynchronize(b.rec_ev));  // the ordered records (pinned)
-            make_children(b, b.defer_R, b.defer_n, *b.defer_rows);
+            b.defer.on = false;
+            if (b.dev_order) FSM_HIP(hipEventSynchronize(b.gpu.rec_ev.ev));  // the ordered records (pinned)
+            make_children(b, b.defer.R, b.defer.n, *b.defer.rows);
             if (b.dev_order) {
                 // the exact child entries (the slab was sized by every record's support)
                 uint64_t exact = 0;
                 for (const ChildInfo& c : b.children) exact += c.cap;
-                if (exact > nb.slab.cap)
+                if (exact > nb.gpu.slab.cap)
                     throw Error(FSM_EDEVICE, "SPADE internal error: root children exceed their slab");
                 nb.E = exact;
                 pend_total = exact;
@@ -4387,7 +4351,7 @@ struct Miner {
             std::swap(nb.cls, b.children);
             std::swap(nb.rank_item, b.child_rank_item);
             std::swap(nb.node_of, b.child_node_of);
-            hp[2] += now_ms() - td;
+            hp[kChildren] += now_ms() - td;
         }
     }
     // the deferred emit check (after a stream sync)
@@ -4402,11 +4366,6 @@ struct Miner {
                                          std::to_string(pend_total));
     }
 
-    // FSM_ROOT_DB=0 keeps the root slab (k_root_count + k_root_write) for every mine (tests, A/B)
-    static bool root_db_env() {
-        const char* v = std::getenv("FSM_ROOT_DB");
-        return !(v && v[0] == '0');
-    }
     // the DB's row positions for the DB-direct root (once per DB); false = a row is too long
     bool ensure_db_pos() {
         if (db->pos_state == 0) {
@@ -4433,7 +4392,7 @@ struct Miner {
     // geometry does not apply: the caller then builds the root slab.
     bool run_root_db(Batch& root, const std::vector<uint32_t>& freq_items, const std::vector<uint32_t>& f1,
                      const std::vector<uint32_t>& rank) {
-        if (!(W == 1 || W == 2 || W == 4 || W == 8) || !root_db_env() || root_atomic() || db->R == 0) return false;
+        if (!windowed_w(W) || !knobs.root_db || knobs.root_atomic || db->R == 0) return false;
         const uint32_t F = uint32_t(freq_items.size());
         root.root = true;
         const F2Geo geo = f2_geometry(root, 2 * F, uint64_t(db->E), uint64_t(db->R));
@@ -4452,36 +4411,36 @@ struct Miner {
                 rk2[u] = 2 * below - 1u;  // wraps to 0xFFFFFFFF below the first frequent item
             }
         }
-        upload_staged(0, root.rk2, rk2.data(), rk2.size() * 4);  // (pinned: the copy does not block the host)
+        upload_staged(0, root.f2.rk2, rk2.data(), rk2.size() * 4);  // (pinned: the copy does not block the host)
         // the unordered-pair layout (W = 1): its own groups over this rank's rows
         uint32_t G = geo.G;
         uint64_t nd = geo.nd;
-        root.f2_tri = false;
-        if (W == 1 && f2_tri_env()) {
+        root.f2.tri = false;
+        if (W == 1 && knobs.f2_tri) {
             std::vector<uint32_t> tab;
             const uint32_t rlo = geo.mlo / 2, rhi = geo.mhi == kNone ? F : std::min(geo.mhi / 2, F);
             const uint32_t TG = tri_tables(F, rlo, rhi, tab);
             if (TG) {
-                upload_staged(1, root.f2_tri_tab, tab.data(), tab.size() * 4);
-                root.f2_tri = true;
-                root.f2_tri_G = TG;
+                upload_staged(1, root.f2.tri_tab, tab.data(), tab.size() * 4);
+                root.f2.tri = true;
+                root.f2.tri_G = TG;
                 G = TG;
                 nd = uint64_t(TG) * geo.nblk;
             }
         }
-        root.mem_db.alloc(std::max<int64_t>(db->E, 1) * 4);
+        root.f2.mem_db.alloc(std::max<int64_t>(db->E, 1) * 4);
         DevBuf cap(nd * 4);
-        root.f2_base.alloc((nd + 1) * 8);
+        root.f2.base.alloc((nd + 1) * 8);
         const size_t tk = clk->begin("k_f2_plan");
         hipLaunchKernelGGL(k_f2_plan_db, dim3(geo.nblk), dim3(kF2Threads), size_t(G) * 4, s,
-                           db->row_off.as<uint32_t>(), db->item.as<uint32_t>(), root.rk2.as<uint32_t>(), geo.R,
+                           db->row_off.as<uint32_t>(), db->item.as<uint32_t>(), root.f2.rk2.as<uint32_t>(), geo.R,
                            geo.rpb, geo.pm, G, geo.nblk, geo.mlo, geo.mhi, cap.as<uint32_t>(), kF2Align - 1,
-                           root.mem_db.as<uint32_t>(), root.f2_tri ? root.f2_tri_tab.as<uint32_t>() : nullptr);
+                           root.f2.mem_db.as<uint32_t>(), root.f2.tri ? root.f2.tri_tab.as<uint32_t>() : nullptr);
         FSM_LAUNCHED("k_f2_plan", s);
         clk->end(tk, int64_t(db->R) * 4 + db->E * 8 + int64_t(nd) * 4);
-        scan_exclusive(cap.as<uint32_t>(), root.f2_base.as<uint64_t>(), nd, s);
+        scan_exclusive(cap.as<uint32_t>(), root.f2.base.as<uint64_t>(), nd, s);
         pend[2] = 0;
-        FSM_HIP(hipMemcpyAsync(&pend[2], root.f2_base.as<uint64_t>() + nd, 8, hipMemcpyDeviceToHost, s));
+        FSM_HIP(hipMemcpyAsync(&pend[2], root.f2.base.as<uint64_t>() + nd, 8, hipMemcpyDeviceToHost, s));
         root_meta(root, freq_items, f1);
         // the root entries: one per (sequence, frequent item), so the frequent items' supports add up to them
         uint64_t E0 = 0;
@@ -4497,12 +4456,12 @@ struct Miner {
         root.R = uint64_t(db->R);
         root.cls[0].cap = E0;
         ctx->stats.root_entries = int64_t(E0);
-        root.f2_planned = true;
-        root.f2_nslots = pend[2];
+        root.f2.planned = true;
+        root.f2.nslots = pend[2];
         root.db_direct = true;
         // the pair keys start now: the host's root bookkeeping (class record, member rows,
         // descriptors) overlaps them (count_and_freq -> root_f2_tri takes the count from here)
-        if (root.f2_tri && !comm) (void)launch_f2_tri(root, f2_geometry(root, 2 * F, E0, uint64_t(db->R)));
+        if (root.f2.tri && !comm) (void)launch_f2_tri(root, f2_geometry(root, 2 * F, E0, uint64_t(db->R)));
         return true;
     }
 
@@ -4555,47 +4514,45 @@ struct Miner {
         FSM_HIP(hipMemcpyAsync(&pend[4], roff.as<uint64_t>() + (r1 - r0), 8, hipMemcpyDeviceToHost, s));
         FSM_HIP(hipMemcpyAsync(&pend[5], flag.p, 4, hipMemcpyDeviceToHost, s));
         const uint64_t Ecap = uint64_t(std::max<int64_t>(db->E, 1));
-        root.slab.alloc(Ecap, W);
-        FSM_HIP(hipMemsetAsync(root.slab.cid.p, 0, Ecap * 4, s));
+        root.gpu.slab.alloc(Ecap, W);
+        FSM_HIP(hipMemsetAsync(root.gpu.slab.cid.p, 0, Ecap * 4, s));
         // the root batch's F2 geometry (its slab is this root slab): plan fused into the write
         const uint32_t F = uint32_t(freq_items.size());
         size_t tk_rw = size_t(-1);
         root.root = true;
         const F2Geo geo = f2_geometry(root, 2 * F, Ecap, r1 - r0);
         if (r1 > r0 && geo.ok) {
-            const SlabPtrs op = root.slab.ptrs();
+            const SlabPtrs op = root.gpu.slab.ptrs();
             DevBuf cap(geo.nd * 4);
-            root.f2_base.alloc((geo.nd + 1) * 8);
+            root.f2.base.alloc((geo.nd + 1) * 8);
             const size_t tk = clk->begin("k_root_write");
-#define FSM_ROOTWP(WW)                                                                                            \
-    hipLaunchKernelGGL(k_root_write_plan<WW>, dim3(geo.nblk), dim3(kF2Threads), size_t(geo.G) * 4, s,              \
-                       db->row_off.as<uint32_t>(), db->item.as<uint32_t>(), db->mask.as<uint64_t>(),               \
-                       d_rank.as<uint32_t>(), geo.R, geo.rpb, roff.as<uint64_t>(), op, geo.pm, geo.G, geo.nblk,    \
-                       geo.mlo, geo.mhi, cap.as<uint32_t>(), kF2Align - 1, uint32_t(W))
-            FSM_W_DISPATCH(W, FSM_ROOTWP)
-#undef FSM_ROOTWP
+            with_width(W, [&](auto w) {
+                hipLaunchKernelGGL(k_root_write_plan<decltype(w)::value>, dim3(geo.nblk), dim3(kF2Threads),
+                                   size_t(geo.G) * 4, s, db->row_off.as<uint32_t>(), db->item.as<uint32_t>(),
+                                   db->mask.as<uint64_t>(), d_rank.as<uint32_t>(), geo.R, geo.rpb, roff.as<uint64_t>(), op,
+                                   geo.pm, geo.G, geo.nblk, geo.mlo, geo.mhi, cap.as<uint32_t>(), kF2Align - 1, uint32_t(W));
+            });
             FSM_LAUNCHED("k_root_write", s);
             clk->end(tk, int64_t(uint64_t(db->E) * (8 + 8 * uint64_t(W)) + geo.nd * 4));
             tk_rw = tk;
-            scan_exclusive(cap.as<uint32_t>(), root.f2_base.as<uint64_t>(), geo.nd, s);
-            FSM_HIP(hipMemcpyAsync(&pend[2], root.f2_base.as<uint64_t>() + geo.nd, 8, hipMemcpyDeviceToHost, s));
-            root.f2_planned = true;
+            scan_exclusive(cap.as<uint32_t>(), root.f2.base.as<uint64_t>(), geo.nd, s);
+            FSM_HIP(hipMemcpyAsync(&pend[2], root.f2.base.as<uint64_t>() + geo.nd, 8, hipMemcpyDeviceToHost, s));
+            root.f2.planned = true;
         } else if (r1 > r0) {
-            const SlabPtrs op = root.slab.ptrs();
+            const SlabPtrs op = root.gpu.slab.ptrs();
             const unsigned grid = unsigned(((r1 - r0) * 64 + kBlock - 1) / kBlock);
             const size_t tk = clk->begin("k_root_write");
-#define FSM_ROOTW(WW)                                                                                         \
-    hipLaunchKernelGGL(k_root_write<WW>, dim3(grid), dim3(kBlock), 0, s, db->row_off.as<uint32_t>(),           \
-                       db->item.as<uint32_t>(), db->mask.as<uint64_t>(), d_rank.as<uint32_t>(), r0, r1,       \
-                       roff.as<uint64_t>(), op, uint32_t(W))
-            FSM_W_DISPATCH(W, FSM_ROOTW)
-#undef FSM_ROOTW
+            with_width(W, [&](auto w) {
+                hipLaunchKernelGGL(k_root_write<decltype(w)::value>, dim3(grid), dim3(kBlock), 0, s,
+                                   db->row_off.as<uint32_t>(), db->item.as<uint32_t>(), db->mask.as<uint64_t>(),
+                                   d_rank.as<uint32_t>(), r0, r1, roff.as<uint64_t>(), op, uint32_t(W));
+            });
             FSM_LAUNCHED("k_root_write", s);
             clk->end(tk, int64_t(uint64_t(db->E) * (8 + 8 * uint64_t(W))));
             tk_rw = tk;
         }
         root_meta(root, freq_items, f1);
-        root.root_rows = std::move(roff);
+        root.f2.root_rows = std::move(roff);
         root.R = r1 - r0;
         sync();
         const uint64_t E0 = pend[4];
@@ -4606,7 +4563,7 @@ struct Miner {
         ctx->stats.root_entries = int64_t(E0);
         ctx->stats.rank_root_slab = int64_t(E0);
         if (tk_rw != size_t(-1)) clk->add_bytes(tk_rw, int64_t(E0 * (16 + 8 * uint64_t(W))));
-        if (root.f2_planned) root.f2_nslots = pend[2];
+        if (root.f2.planned) root.f2.nslots = pend[2];
     }
 
 };
@@ -4751,7 +4708,7 @@ void spade_mine(fsm_ctx* ctx, fsm_db* db, double support, fsm_patterns** out) {
     const double t0 = now_ms();
     SpadeDevDB* d = db->spade_dev;
     const int64_t total = db->spade.total;
-    Miner mn{ctx, d, ctx->stream, d->W, 1, 0, {}};
+    Miner mn{SpadeKnobs::from_env(), ctx, d, ctx->stream, d->W, 1, 0, {}};
     KernelClock clock(ctx->stream);
     ClockScope clock_scope(&clock);
     mn.clk = &clock;
@@ -4877,7 +4834,7 @@ void spade_mine(fsm_ctx* ctx, fsm_db* db, double support, fsm_patterns** out) {
             throw Error(FSM_EDEVICE, "SPADE internal error: lattice depth " + std::to_string(nb->depth) +
                                          " exceeds the longest sequence (" + std::to_string(db->spade.max_occ) + ")");
         mn.emit(top, g, *nb);
-        if (top.next_group >= top.groups.size() && top.claim_key < 0) {
+        if (top.next_group >= top.groups.size() && top.claim.key < 0) {
             // parent fully emitted: release it before descending (a claiming root stays until
             // its claims run out)
             pop();
@@ -4895,19 +4852,17 @@ void spade_mine(fsm_ctx* ctx, fsm_db* db, double support, fsm_patterns** out) {
         ctx->stats.pair_tests = int64_t(tests);
     });
     ctx->stats.ms_lattice = now_ms() - t2;
-    if (const char* v = std::getenv("FSM_HOST_TRACE"); v && v[0] == '1')
-        std::fprintf(stderr, "[fsm host] f2 sort %.3f, kids %.3f, children %.3f, groups %.3f, emit tables %.3f, "
-                     "slab alloc %.3f, count prep %.3f, count+extract %.3f, gpu wait %.3f ms\n", mn.hp[0], mn.hp[1],
-                     mn.hp[2], mn.hp[3], mn.hp[4], mn.hp[5], mn.hp[6], mn.hp[7], mn.wait_ms);
-    if (const char* v = std::getenv("FSM_HOST_TRACE"); v && v[0] == '1') {
-        std::fprintf(stderr, "[fsm host laps]");
-        for (int i = 0; i < 16; ++i) std::fprintf(stderr, " %d:%.2f", i, mn.hq[i]);
+    if (mn.knobs.host_trace == 1) {
+        std::fprintf(stderr, "[fsm host]");
+        for (int i = 0; i < Miner::kPhases; ++i) std::fprintf(stderr, " %s %.3f,", Miner::kPhaseName[i], mn.hp[i]);
+        std::fprintf(stderr, " gpu wait %.3f ms\n[fsm host laps]", mn.wait_ms);
+        for (int i = 0; i < Miner::kLaps; ++i) std::fprintf(stderr, " %d:%.2f", i, mn.hq[i]);
         std::fprintf(stderr, "\n");
     }
     mn.run_or_defer([&] { clock.finish(ctx->kstats); });
     for (const fsm_kernel_stat& k : ctx->kstats) {
         const std::string nm = k.name;
-        if (nm == "k_count" || nm.rfind("k_root_keys", 0) == 0 || nm == "k_group_count") ctx->stats.ms_count_kernel += k.ms;
+        if (nm == "k_count") ctx->stats.ms_count_kernel += k.ms;
         if (nm.rfind("k_emit", 0) == 0) ctx->stats.ms_emit_kernel += k.ms;
     }
 

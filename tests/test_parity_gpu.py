@@ -425,7 +425,7 @@ def _wide_runs_db(seed=5, n=600):
 
 
 @pytest.mark.parametrize("path", ["onepass", "overflow-all", "overflow-some", "chunk", "host-child-of", "device-child-of", "host-kids",
-                                  "host-order", "no-defer"])
+                                  "host-order", "no-defer", "host-threads"])
 @pytest.mark.parametrize("shape", ["quest", "sign", "bible", "wide"])
 def test_emit_paths_agree(eng, path, shape, monkeypatch):
     """Child-run emission: the window kernel k_emit2 (W = 1: runs of <= 64
@@ -436,7 +436,9 @@ def test_emit_paths_agree(eng, path, shape, monkeypatch):
     table (FSM_CHILD_OF=host, or device: k_child_flag / scan / k_child_of), and
     both orderings of a one-group batch's records (default: on the device, k_rk_*;
     FSM_DEVORDER=0: on the host) with the children built after the emit launch or,
-    FSM_EMIT_DEFER=0, before it."""
+    FSM_EMIT_DEFER=0, before it.  host-threads (FSM_HOST_PAR_MIN=1) builds the
+    children, the kid table and the deferral sums on the host thread pool, as
+    batches of 2^16 records and more do."""
     from oracle import oracle
     from tools import gen
     if path == "overflow-all":
@@ -455,6 +457,8 @@ def test_emit_paths_agree(eng, path, shape, monkeypatch):
         monkeypatch.setenv("FSM_DEVORDER", "0")
     elif path == "no-defer":
         monkeypatch.setenv("FSM_EMIT_DEFER", "0")
+    elif path == "host-threads":
+        monkeypatch.setenv("FSM_HOST_PAR_MIN", "1")
     ds, sup, o = shape_case(shape)
     pats, meta, st = gpu_spade(eng, None, sup, tokens=ds)
     assert pats == o["patterns"] and st["joins"] == o["joins"]
