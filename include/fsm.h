@@ -286,6 +286,22 @@ void fsm_patterns_free(fsm_patterns* p);
 #define FSM_KEEP_MAXIMAL 2
 int fsm_patterns_filter(fsm_ctx* ctx, const fsm_patterns* in, int32_t keep, fsm_patterns** out, int64_t* kept_idx);
 
+/* Supports of GIVEN patterns in a resident SPADE DB, counted on the GPU by definition
+ * (P is contained in a sequence iff eids e1 < ... < em exist with Xk a subset
+ * of the sequence's itemset at ek; support = number of distinct sequence ids containing P).
+ * `in` is borrowed, never modified and may be caller-built: its support (may be NULL),
+ * total and minsup are ignored, its items are item VALUES as in a mined result, and it is
+ * checked before any device work by the CSR rules of fsm_patterns_filter (FSM_EINVAL;
+ * n or n_items >= 2^32 - 2: FSM_ELIMIT; a db not of FSM_MODE_SPADE: FSM_EINVAL).  A failed
+ * check leaves support_out untouched.  A pattern that cannot match (an item the DB does not
+ * hold, more itemsets than the DB has eids, more items than any row) gets 0, not an error;
+ * equal patterns are separate entries with equal counts; n == 0 succeeds and writes
+ * nothing.  The first call on a DB builds its item -> rows index (8 bytes per DB entry,
+ * freed with the DB).  A group context (ndevices > 1) counts on its rank 0's replica; with
+ * nranks > 1 each process counts on its own.  fsm_stats is left as it is; the kernel
+ * statistics become this call's (k_ps_*). */
+int fsm_patterns_support(fsm_ctx* ctx, fsm_db* db, const fsm_patterns* in, int32_t* support_out /* [in->n] */);
+
 int fsm_tsr_mine(fsm_ctx* ctx, fsm_db* db, int32_t k, double minconf, fsm_rules** out);
 void fsm_rules_free(fsm_rules* r);
 

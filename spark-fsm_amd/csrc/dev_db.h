@@ -19,6 +19,14 @@ struct SpadeDevDB {
     // -1 = a row exceeds 65535 entries (that DB keeps the root slab)
     fsm::DevBuf pos;      // u32 [E]
     int pos_state = 0;
+    // the vertical index (pattern_support.hip): item i's entries are vert[vert_off[i] ..
+    // vert_off[i+1]), each (row, entry index); made by the first fsm_patterns_support on this
+    // DB (vert_state 0 = not made, 1 = made), in no particular order inside a list.  The host
+    // copy of vert_off gives the list lengths (= F1 supports) the pivot choice reads
+    fsm::DevBuf vert_off;  // u32 [U+1]
+    fsm::DevBuf vert;      // uint2 [E]
+    std::vector<uint32_t> vert_off_host;
+    int vert_state = 0;
 };
 
 // TSR: horizontal rows (sid = row) of (item, first, last itemset index),

@@ -326,6 +326,13 @@ void tsr_release(fsm_db* db);
 void tsr_mine(fsm_ctx* ctx, fsm_db* db, int32_t k, double minconf, fsm_rules** out);
 // closed / maximal filter of a complete frequent set (pattern_filter.hip); keep is validated by the caller
 void patterns_filter(fsm_ctx* ctx, const fsm_patterns* in, int32_t keep, fsm_patterns** out, int64_t* kept_idx);
+// the CSR checks the filter and the support count share (pattern_filter.hip): FSM_EINVAL with
+// `who` in front of the message; ioff[p] = first flat item of pattern p (n + 1 entries),
+// start[i] = item i opens an itemset
+void pf_validate(const fsm_patterns* in, const char* who, bool need_support, std::vector<uint32_t>& ioff,
+                 std::vector<uint8_t>& start);
+// supports of given patterns in a resident SPADE DB (pattern_support.hip)
+void patterns_support(fsm_ctx* ctx, fsm_db* db, const fsm_patterns* in, int32_t* support_out);
 // FSM_HOST_PROF=<file>: SIGPROF sampling of the host side of a mine (host_prof.cpp)
 bool host_prof_start();
 void host_prof_stop();

@@ -192,53 +192,6 @@ struct ResultGuard {
     }
 };
 
-// The CSR checks of fsm_patterns_filter, and the two compact arrays the kernels read
-// instead of the 64-bit offsets: ioff[p] = first flat item of pattern p, start[i] = item
-// i opens an itemset.  Split over the host threads by patterns.
-void pf_validate(const fsm_patterns* in, std::vector<uint32_t>& ioff, std::vector<uint8_t>& start) {
-    const int64_t n = in->n, ns = in->n_sets, ni = in->n_items;
-    if (!in->support || !in->pat_off || !in->set_off || !in->items)
-        throw Error(FSM_EINVAL, "fsm_patterns_filter: null pattern arrays");
-    if (ns < n || ni < ns) throw Error(FSM_EINVAL, "fsm_patterns_filter: fewer itemsets than patterns or items than itemsets");
-    if (in->pat_off[0] != 0 || in->pat_off[n] != ns)
-        throw Error(FSM_EINVAL, "fsm_patterns_filter: pat_off must run from 0 to n_sets");
-    if (in->set_off[0] != 0 || in->set_off[ns] != ni)
-        throw Error(FSM_EINVAL, "fsm_patterns_filter: set_off must run from 0 to n_items");
-    ioff.resize(size_t(n) + 1);
-    start.resize(size_t(ni));
-    const int64_t nthr = n >= 65536 ? host_threads() : 1;
-    std::vector<int64_t> bad(size_t(nthr), -1);
-    std::vector<const char*> why(size_t(nthr), nullptr);
-    par_slices(nthr, n, [&](int64_t t, int64_t p0, int64_t p1) {
-        auto fail = [&](int64_t p, const char* m) {
-            bad[size_t(t)] = p;
-            why[size_t(t)] = m;
-        };
-        for (int64_t p = p0; p < p1; ++p) {
-            const int64_t s0 = in->pat_off[p], s1 = in->pat_off[p + 1];
-            if (s0 < 0 || s1 > ns || s0 > s1) return fail(p, "pat_off is not monotone");
-            if (s0 == s1) return fail(p, "a pattern without itemsets");
-            if (in->set_off[s0] < 0 || in->set_off[s0] > ni) return fail(p, "set_off is not monotone");
-            ioff[size_t(p)] = uint32_t(in->set_off[s0]);
-            for (int64_t s = s0; s < s1; ++s) {
-                const int64_t i0 = in->set_off[s], i1 = in->set_off[s + 1];
-                if (i0 < 0 || i1 > ni || i0 > i1) return fail(p, "set_off is not monotone");
-                if (i0 == i1) return fail(p, "an empty itemset");
-                start[size_t(i0)] = 1;
-                for (int64_t i = i0 + 1; i < i1; ++i) {
-                    if (in->items[i - 1] >= in->items[i]) return fail(p, "items of an itemset are not strictly ascending");
-                    start[size_t(i)] = 0;
-                }
-            }
-        }
-    });
-    for (int64_t t = 0; t < nthr; ++t)
-        if (bad[size_t(t)] >= 0)
-            throw Error(FSM_EINVAL, std::string("fsm_patterns_filter: ") + why[size_t(t)] + " (pattern " +
-                                        std::to_string(bad[size_t(t)]) + ")");
-    ioff[size_t(n)] = uint32_t(ni);
-}
-
 // drop[] -> the kept patterns in input order (two passes over pattern slices: sizes, fill)
 void pf_compact(const fsm_patterns* in, const uint8_t* drop, fsm_patterns* out, int64_t* kept_idx) {
     const int64_t n = in->n;
@@ -290,6 +243,55 @@ void pf_compact(const fsm_patterns* in, const uint8_t* drop, fsm_patterns* out, 
 
 }  // namespace
 
+// The CSR checks of fsm_patterns_filter and fsm_patterns_support (`who` names the caller in
+// the messages; fsm_patterns_support takes a NULL support array), and the two compact arrays
+// the kernels read instead of the 64-bit offsets: ioff[p] = first flat item of pattern p,
+// start[i] = item i opens an itemset.  Split over the host threads by patterns.
+void pf_validate(const fsm_patterns* in, const char* who, bool need_support, std::vector<uint32_t>& ioff,
+                 std::vector<uint8_t>& start) {
+    const std::string pre = std::string(who) + ": ";
+    const int64_t n = in->n, ns = in->n_sets, ni = in->n_items;
+    if ((need_support && !in->support) || !in->pat_off || !in->set_off || !in->items)
+        throw Error(FSM_EINVAL, pre + "null pattern arrays");
+    if (ns < n || ni < ns) throw Error(FSM_EINVAL, pre + "fewer itemsets than patterns or items than itemsets");
+    if (in->pat_off[0] != 0 || in->pat_off[n] != ns)
+        throw Error(FSM_EINVAL, pre + "pat_off must run from 0 to n_sets");
+    if (in->set_off[0] != 0 || in->set_off[ns] != ni)
+        throw Error(FSM_EINVAL, pre + "set_off must run from 0 to n_items");
+    ioff.resize(size_t(n) + 1);
+    start.resize(size_t(ni));
+    const int64_t nthr = n >= 65536 ? host_threads() : 1;
+    std::vector<int64_t> bad(size_t(nthr), -1);
+    std::vector<const char*> why(size_t(nthr), nullptr);
+    par_slices(nthr, n, [&](int64_t t, int64_t p0, int64_t p1) {
+        auto fail = [&](int64_t p, const char* m) {
+            bad[size_t(t)] = p;
+            why[size_t(t)] = m;
+        };
+        for (int64_t p = p0; p < p1; ++p) {
+            const int64_t s0 = in->pat_off[p], s1 = in->pat_off[p + 1];
+            if (s0 < 0 || s1 > ns || s0 > s1) return fail(p, "pat_off is not monotone");
+            if (s0 == s1) return fail(p, "a pattern without itemsets");
+            if (in->set_off[s0] < 0 || in->set_off[s0] > ni) return fail(p, "set_off is not monotone");
+            ioff[size_t(p)] = uint32_t(in->set_off[s0]);
+            for (int64_t s = s0; s < s1; ++s) {
+                const int64_t i0 = in->set_off[s], i1 = in->set_off[s + 1];
+                if (i0 < 0 || i1 > ni || i0 > i1) return fail(p, "set_off is not monotone");
+                if (i0 == i1) return fail(p, "an empty itemset");
+                start[size_t(i0)] = 1;
+                for (int64_t i = i0 + 1; i < i1; ++i) {
+                    if (in->items[i - 1] >= in->items[i]) return fail(p, "items of an itemset are not strictly ascending");
+                    start[size_t(i)] = 0;
+                }
+            }
+        }
+    });
+    for (int64_t t = 0; t < nthr; ++t)
+        if (bad[size_t(t)] >= 0)
+            throw Error(FSM_EINVAL, pre + why[size_t(t)] + " (pattern " + std::to_string(bad[size_t(t)]) + ")");
+    ioff[size_t(n)] = uint32_t(ni);
+}
+
 void patterns_filter(fsm_ctx* ctx, const fsm_patterns* in, int32_t keep, fsm_patterns** out, int64_t* kept_idx) {
     const int64_t n = in->n, ni = in->n_items;
     if (n < 0 || in->n_sets < 0 || ni < 0) throw Error(FSM_EINVAL, "fsm_patterns_filter: negative sizes");
@@ -314,7 +316,7 @@ void patterns_filter(fsm_ctx* ctx, const fsm_patterns* in, int32_t keep, fsm_pat
     }
     std::vector<uint32_t> ioff;
     std::vector<uint8_t> start, drop;
-    pf_validate(in, ioff, start);
+    pf_validate(in, "fsm_patterns_filter", true, ioff, start);
 
     const int closed = keep == FSM_KEEP_CLOSED;
     const uint64_t hmask = pf_hash_mask();

@@ -72,6 +72,20 @@ def extract_rdd_patterns(dataset, support, dfs=True, stats=True, engine=None, ke
     return [Pattern(s, sup) for s, sup in pats]
 
 
+def pattern_supports(records_or_db, patterns, engine=None):
+    """The supports of GIVEN patterns (Engine.pattern_supports' forms) in a dataset of
+    (sid, spmf_line) pairs, or in a SPADE DB an engine already holds (an extension: the
+    reference can only mine) -> np.ndarray[int32], one count per pattern."""
+    if hasattr(records_or_db, "handle"):
+        return records_or_db.engine.pattern_supports(records_or_db, patterns)
+    eng = engine or default_engine()
+    db = eng.db_from_spmf(list(records_or_db), MODE_SPADE)
+    try:
+        return eng.pattern_supports(db, patterns)
+    finally:
+        db.free()
+
+
 def extract_rdd_rules(dataset, k, minconf, engine=None):
     """TSR.extractRDDRules (TSR.scala:31-107) on the GPU engine."""
     eng = engine or default_engine()

@@ -171,6 +171,43 @@ class Engine:
                              len(so) - 1, len(it), 0, 0)
         return self._filter(pats, keep, copy)
 
+    def pattern_supports(self, db, patterns):
+        """fsm_patterns_support: the supports of GIVEN patterns in a resident SPADE DB,
+        counted on the GPU by definition -> np.ndarray[int32], one count per pattern.
+
+        patterns is a CSR tuple (support_or_None, pat_off, set_off, items) like spade_csr's
+        (the supports are ignored), or a list of itemset tuples such as ((1,), (3, 4)), or
+        a list of (itemsets, support) pairs as Engine.spade returns them.  Items are item
+        values; a pattern that cannot match (an unknown item, more itemsets than the DB
+        has eids) counts 0.  The first call on a DB builds its item -> rows index."""
+        flat = (np.ndarray, list)
+        if (isinstance(patterns, tuple) and len(patterns) == 4 and (patterns[0] is None or isinstance(patterns[0], flat))
+                and isinstance(patterns[1], flat) and (len(patterns[1]) == 0 or not hasattr(patterns[1][0], "__len__"))):
+            _sup, po, so, it = patterns
+        else:
+            po, so, it = [0], [0], []
+            for pat in patterns:
+                # (itemsets, support) pairs carry an int second; an itemset tuple holds tuples only
+                sets = pat[0] if len(pat) == 2 and not hasattr(pat[1], "__len__") else pat
+                for X in sets:
+                    it.extend(X)
+                    so.append(len(it))
+                po.append(len(so) - 1)
+        po = np.ascontiguousarray(po, np.int64)
+        so = np.ascontiguousarray(so, np.int64)
+        it = np.ascontiguousarray(it, np.int32)
+        if len(po) < 1 or len(so) < 1:
+            raise ValueError("pat_off and set_off must have at least one entry")
+        n = len(po) - 1
+        P = ctypes.POINTER
+        pats = _lib.Patterns(n, None, po.ctypes.data_as(P(ctypes.c_int64)), so.ctypes.data_as(P(ctypes.c_int64)),
+                             it.ctypes.data_as(P(ctypes.c_int32)), len(so) - 1, len(it), 0, 0)
+        out = np.zeros(n, np.int32)
+        buf = out if n else np.zeros(1, np.int32)
+        check(self._L.fsm_patterns_support(self._ctx, db.handle, ctypes.byref(pats),
+                                           buf.ctypes.data_as(P(ctypes.c_int32))), self._ctx)
+        return out
+
     def spade_csr(self, db, support, dfs=True, copy=False, keep="all"):
         """fsm_spade_mine -> CSR numpy arrays (support, pat_off, set_off, items), meta.
 
