@@ -11,9 +11,9 @@ TEST INFRASTRUCTURE ONLY (plain Python, no GPU).  Two ideas:
   (a 64-entry run at lane 0, a run that starts at range - 1, ...).
 
 Families: `tight_spade` (hub sequences), `wide_mask_db` (one sequence of E
-itemsets), `big_row_db` (one DB row of n entries), `tsr_long_rows`,
-`tsr_sid_edges`, and `k0_image`, the DB image by definition from the token
-rules (SPADE.scala:53-106, :151-210; TSR.scala:52-94, :109-143); and the TSR
+itemsets), `word_sweep_db` (one decision on every word boundary of the mask),
+`big_row_db` (one DB row of n entries), `tsr_long_rows`, `tsr_sid_edges`,
+and `k0_image`, the DB image by definition from the token rules (SPADE.scala:53-106, :151-210; TSR.scala:52-94, :109-143); and the TSR
 families placed on the expansion kernels' constants (`tsr_constants`, read
 from tsr_engine.hip): `tsr_probe_edges`, `tsr_kid_edges`, `tsr_chain`,
 `tsr_pair_edges`.
@@ -124,7 +124,11 @@ class TightSpade(EdgeDB):
         return sum(len({t for t in r if t >= 0} & freq) for r in self.rows)
 
 
-def tight_spade(lengths, per_set=1, lead=0, prefix=0, pad=0, noise=0, dup=False, filler=0, hub_last=False, seed=1):
+STRETCH_BASE = 1 << 18  # values of the itemsets `stretch` adds: above every item of a stretched hub family
+
+
+def tight_spade(lengths, per_set=1, lead=0, prefix=0, pad=0, noise=0, dup=False, filler=0, hub_last=False, seed=1,
+                stretch=0):
     """The hub family.  For each n in `lengths` one hub sequence holds n fresh
     items, `per_set` per itemset, in shuffled order (rank is not position).
     Each item has one private single-item sequence (support 2); a few pairs
@@ -144,6 +148,10 @@ def tight_spade(lengths, per_set=1, lead=0, prefix=0, pad=0, noise=0, dup=False,
     noise = m   m infrequent items interleaved (by value and by itemset) in
                 every hub: the DB row grows past its frequent entries
     hub_last    the last hub is the last sequence (its runs end at E)
+    stretch = T every hub sequence has exactly T itemsets: unique infrequent one-item
+                itemsets go between the hub's own (its first stays right behind the
+                prefix, its last becomes itemset T - 1), so the hub's eids spread
+                over all the words of a mask of ceil(T / 64) words
     """
     rng = random.Random(seed)
     lengths = list(lengths)
@@ -158,7 +166,7 @@ def tight_spade(lengths, per_set=1, lead=0, prefix=0, pad=0, noise=0, dup=False,
     rows, hub_rows, hub_items, rest = [_row(pre) for _ in range(pad)] if d else [], [], [], []
     assert d or not pad
     singles = {f: 2 for f in fill_items}
-    selected, tail, fi = {}, [], 0
+    selected, tail, fi, nstretch = {}, [], 0, 0
     for n, j in zip(lengths, leads):
         items = [base + 2 * i for i in range(n)]
         noise_items = [base + 2 * (i * n // max(noise, 1)) + 1 for i in range(noise)]
@@ -200,6 +208,13 @@ def tight_spade(lengths, per_set=1, lead=0, prefix=0, pad=0, noise=0, dup=False,
         fi += j
         hub_rows.append(len(rows))
         hub_items.append(items)
+        if stretch:
+            T, n0 = stretch - d, len(sets)
+            assert T >= n0, "the hub has more itemsets than `stretch`"
+            at = {(k * (T - 1) // (n0 - 1) if n0 > 1 else 0): s for k, s in enumerate(sets)}
+            assert len(at) == n0
+            sets = [at[k] if k in at else [STRETCH_BASE + nstretch + k] for k in range(T)]
+            nstretch += T
         rows.append(_row(pre + sets))
     rest_rows = fill_rows[fi:] + tail
     rng.shuffle(rest_rows)
@@ -210,9 +225,10 @@ def tight_spade(lengths, per_set=1, lead=0, prefix=0, pad=0, noise=0, dup=False,
         rows.append(hub)
     else:
         rows.extend(rest_rows)
+    assert not stretch or base <= STRETCH_BASE
     db = TightSpade(rows, "tight%s/%d" % (lengths, per_set))
     db.kw = dict(lengths=lengths, per_set=per_set, lead=lead, prefix=prefix, pad=pad, noise=noise, dup=dup,
-                 filler=filler, hub_last=hub_last, seed=seed)
+                 filler=filler, hub_last=hub_last, seed=seed, stretch=stretch)
     db.selected, db.singles, db.prefix_items = selected, singles, list(range(1, d + 1))
     db.hub_rows, db.hub_items, db.rest_sample = hub_rows, hub_items, rest
     return db
@@ -404,6 +420,174 @@ def wide_mask_db(E, shared_last=True):
     return db
 
 
+class WordSweep(Planted):
+    """word_sweep_db's result.
+    t2, t1     the decisions (patterns) that hold / do not hold in S: support exactly 2 / exactly 1
+    boundary   {decision: k}, gadget {decision: label}
+    ks, eids   the boundaries swept, and {item: eids in S}"""
+
+    def words_of(self, patterns):
+        """The boundaries (word indexes) of the decisions that share a planted item with any of
+        `patterns`: where to look when a comparison fails."""
+        own = {}
+        for p, k in self.boundary.items():
+            for s in p:
+                for it in s:
+                    own[it] = (k, self.gadget[p])
+        return sorted({own[it] for p in patterns for s in p for it in s if it in own})
+
+
+def _eids_of(eids, pattern):
+    """The first eid at which `pattern` ends in a sequence given as {item: eids}, or None: greedy
+    by definition (each itemset at the earliest eid after the one before that holds all its items)."""
+    prev = -1
+    for s in pattern:
+        common = set(eids.get(s[0], ()))
+        for it in s[1:]:
+            common &= set(eids.get(it, ()))
+        later = [e for e in common if e > prev]
+        if not later:
+            return None
+        prev = min(later)
+    return prev
+
+
+def _sub_patterns(p):
+    """Every non-empty sub-pattern of p (items removed, empty itemsets dropped)."""
+    flat = [(k, it) for k, s in enumerate(p) for it in s]
+    out = set()
+    for bits in range(1, 1 << len(flat)):
+        sets = {}
+        for j, (k, it) in enumerate(flat):
+            if bits >> j & 1:
+                sets.setdefault(k, []).append(it)
+        out.add(tuple(tuple(sets[k]) for k in sorted(sets)))
+    return out
+
+
+def prefix_parents(p):
+    """The two prefix-class parents of a pattern of two or more items: p without its last item,
+    and p without the item before it."""
+    flat = [(k, it) for k, s in enumerate(p) for it in s]
+    out = []
+    for drop in (len(flat) - 1, len(flat) - 2):
+        sets = {}
+        for j, (k, it) in enumerate(flat):
+            if j != drop:
+                sets.setdefault(k, []).append(it)
+        out.append(tuple(tuple(sets[k]) for k in sorted(sets)))
+    return out
+
+
+def word_sweep_db(W, ks=None, E=None):
+    """One sequence S of E itemsets (default 64 W: W mask words), one unique infrequent item in
+    each, and for every word boundary k in `ks` (default 1 .. W - 1) a set of gadgets around
+    b = 64 k - 1, the last bit of word k - 1 (b + 1 is the first bit of word k).  d is a decoy eid
+    in an earlier word (two words back where there is one, otherwise in word 0), d2 = d + 3.
+
+    A gadget uses fresh items and makes ONE decision, a pattern p whose only other sequence is p
+    itself: its support is exactly 2 if S holds p (`t2`) and exactly 1 if not (`t1`), every one of
+    its items has support 2, and both its prefix-class parents hold in S (support 2), so the
+    lattice reaches the decision through tight parents.  x@e: item x sits at eid e of S.
+
+    G1a  a@b, c@b+1: a -> c holds          (temporal count across the boundary)
+    G1b  a@b, c@b+1: c -> a does not
+    G1c  a@b, c@b:   a -> c does not        (the same eid is not "after")
+    G2a  p@{d, b+1}, q@b+1: (p q) holds     (the only common bit is in word k)
+    G2b  p@{d, b+1}, q@b: (p q) does not    (the eid ranges overlap, the AND is empty)
+    G3   x@b, y@{d, b+1}, z@b+1: x -> y -> z does not  (temporal child: bits <= lo cleared, its new
+         lo found in word k; an uncleared decoy makes it hold)
+    G4   the same with z@b+2: holds
+    G5a  w@d, p@{d2, b+1}, q@b+1, r@b+1: w -> (p q) -> r does not  (the child of an equality join
+         as the owner of a temporal join)
+    G5b  the same with r@b+2: holds
+    G6a  x@b, y@{b, b+1}, z@b+1: x -> y -> z does not  (the partner's bit AT lo is cleared too: lo
+         the last bit of word k - 1, the whole word goes)
+    G6b  x@b+1, y@{b+1, b+2}, z@b+2: the same with lo the first bit of word k
+    G7   x@d, y@{b, b+2}, z@b+1: x -> y -> z holds  (the child's lo is the last bit of word k - 1
+         while word k holds a later bit)
+    G8   x@b+1, y@{d, 64 (k+1)}, z@64 (k+1): x -> y -> z does not  (lo in word k, the partner's
+         only later bit in word k + 1: word k + 1 is kept whole, the new lo found there)
+    G9a  x@d, y@{d2, b+1}, q@b+1: x -> (y q) holds  (a temporal child keeps its bit in word k,
+         and its hi there passes the range prefilter)
+    G9b  the same with q@b: does not
+    Gadgets that need eid b + 2 (or 64 (k + 1)) are left out where S ends before it."""
+    E = 64 * W if E is None else E
+    ks = list(range(1, W)) if ks is None else list(ks)
+    big = [[1000000 + e] for e in range(E)]
+    eids, t2, t1, boundary, gadget = {}, [], [], {}, {}
+    nxt = [1]
+
+    def fresh(*at):
+        out = []
+        for es in at:
+            it = nxt[0]
+            nxt[0] += 1
+            es = (es,) if isinstance(es, int) else tuple(es)
+            assert all(0 <= e < E for e in es)
+            eids[it] = sorted(es)
+            for e in es:
+                big[e].append(it)
+            out.append(it)
+        return out
+
+    def decide(k, label, p, holds):
+        assert (_eids_of(eids, p) is not None) == holds, (k, label)
+        (t2 if holds else t1).append(p)
+        boundary[p], gadget[p] = k, label
+
+    for k in ks:
+        b = 64 * k - 1
+        assert 0 < b and b + 1 < E
+        d = 64 * (k - 2) + 5 if k >= 3 else 5
+        d2 = d + 3
+        a, c = fresh(b, b + 1)
+        decide(k, "G1a", ((a,), (c,)), True)
+        a, c = fresh(b, b + 1)
+        decide(k, "G1b", ((c,), (a,)), False)
+        a, c = fresh(b, b)
+        decide(k, "G1c", ((a,), (c,)), False)
+        p, q = fresh((d, b + 1), b + 1)
+        decide(k, "G2a", ((p, q),), True)
+        p, q = fresh((d, b + 1), b)
+        decide(k, "G2b", ((p, q),), False)
+        x, y, z = fresh(b, (d, b + 1), b + 1)
+        decide(k, "G3", ((x,), (y,), (z,)), False)
+        w, p, q, r = fresh(d, (d2, b + 1), b + 1, b + 1)
+        decide(k, "G5a", ((w,), (p, q), (r,)), False)
+        x, y, z = fresh(b, (b, b + 1), b + 1)
+        decide(k, "G6a", ((x,), (y,), (z,)), False)
+        x, y, q = fresh(d, (d2, b + 1), b + 1)
+        decide(k, "G9a", ((x,), (y, q)), True)
+        x, y, q = fresh(d, (d2, b + 1), b)
+        decide(k, "G9b", ((x,), (y, q)), False)
+        if b + 2 < E:
+            x, y, z = fresh(b, (d, b + 1), b + 2)
+            decide(k, "G4", ((x,), (y,), (z,)), True)
+            w, p, q, r = fresh(d, (d2, b + 1), b + 1, b + 2)
+            decide(k, "G5b", ((w,), (p, q), (r,)), True)
+            x, y, z = fresh(b + 1, (b + 1, b + 2), b + 2)
+            decide(k, "G6b", ((x,), (y,), (z,)), False)
+            x, y, z = fresh(d, (b, b + 2), b + 1)
+            decide(k, "G7", ((x,), (y,), (z,)), True)
+        if 64 * (k + 1) < E:
+            x, y, z = fresh(b + 1, (d, 64 * (k + 1)), 64 * (k + 1))
+            decide(k, "G8", ((x,), (y,), (z,)), False)
+    decisions = t2 + t1
+    rows = [_row([sorted(s) for s in big])] + [_row([list(s) for s in p]) for p in decisions]
+    db = WordSweep(rows, "word-sweep-W%d-E%d" % (W, E))
+    db.singles = {it: 2 for it in eids}
+    # closed form: a multi-item pattern over planted items is held by one private sequence at
+    # most (the gadgets share no item), so it is frequent iff it is a sub-pattern of a decision and S holds it
+    db.selected = {}
+    for p in decisions:
+        for q in _sub_patterns(p):
+            if sum(len(s) for s in q) > 1 and _eids_of(eids, q) is not None:
+                db.selected[q] = 2
+    db.W, db.E, db.ks, db.eids, db.t2, db.t1, db.boundary, db.gadget = W, E, ks, eids, t2, t1, boundary, gadget
+    return db
+
+
 def big_row_db(n, nsets=60):
     """One DB row of exactly n distinct items over `nsets` itemsets (W = 1), three
     of them frequent: the lowest, the middle and the highest value of the row."""
@@ -591,31 +775,34 @@ def f2_cases():
 
 
 def lattice_cases(w):
-    """Family 2, lattice windows at mask width w (1 or 2), prefix = 2:
+    """Family 2, lattice windows at mask width w (1, 2, 4 or 8), prefix = 2:
     (name, db, level, claim) where claim is a dict of geometry facts to assert:
-    {"length": L} for hub 0's run at `level`, {"start": s}, {"end_is_E": True}."""
+    {"length": L} for hub 0's run at `level`, {"start": s}, {"end_is_E": True}.
+    At w = 4 and 8 every hub is stretched to exactly 64 w itemsets (tight_spade's
+    `stretch`): its entries' eids lie in every word of the mask."""
     def make():
         out = []
         d = 2
+        st = 64 * w if w > 2 else 0
         # run lengths: a hub of n items is a run of n + 2 in the root, n + 1 in [A1], n in [A1 -> A2]
         ns = sorted({L - k for L in LATTICE_SHORT + LATTICE_LONG for k in (0, 1)})
         if w == 1:
             out.append(("lengths", tight_spade(ns, per_set=5, prefix=d, seed=5), 1,
                         {"lengths": [n + 1 for n in ns]}))
-        else:  # 64 < itemsets <= 128 in the longest sequence
-            out.append(("lengths", tight_spade(ns, per_set=3, prefix=d, seed=5), 1,
+        else:  # 64 < itemsets <= 128 in the longest sequence (w = 2); per_set = 3: 257 items fit 254 itemsets
+            out.append(("lengths", tight_spade(ns, per_set=3, prefix=d, seed=5, stretch=st), 1,
                         {"lengths": [n + 1 for n in ns]}))
         n = 63  # a 64-entry run in [A1]
         ps = 3 if w == 1 else 1  # per_set = 1: 65 itemsets, two mask words
         for r in range(64, 513, 64):
             for start in (r - 63, r - 1, r):
                 lead, pad = place(1, start, d)
-                db = tight_spade([n], per_set=ps, prefix=d, lead=lead, pad=pad, seed=start)
+                db = tight_spade([n], per_set=ps, prefix=d, lead=lead, pad=pad, seed=start, stretch=st)
                 out.append(("L1-start%d" % start, db, 1, {"start": start, "length": 64}))
                 if w == 1:  # the same placement in the root class (no prefix: every filler run is one entry)
                     db = tight_spade([64], per_set=ps, lead=start, seed=start)
                     out.append(("L0-start%d" % start, db, 0, {"start": start, "length": 64}))
-        db = tight_spade([20, n], per_set=ps, prefix=d, lead=[3, 5], hub_last=True, seed=6)
+        db = tight_spade([20, n], per_set=ps, prefix=d, lead=[3, 5], hub_last=True, seed=6, stretch=st)
         out.append(("hub-last", db, 1, {"end_is_E": True, "length": 64}))
         return out
     return _cached(("lattice", w), make)
@@ -680,6 +867,23 @@ def one_row_group_cases():
 
 def mask_cases():
     return _cached("mask", lambda: [(E, W, wide_mask_db(E, shared_last=E != 4096)) for E, W in zip(MASK_E, MASK_W)])
+
+
+SWEEP_W = (2, 4, 8, 16, 32, 64, 128, 256, 512, 1024)
+
+
+def sweep_ks(W):
+    """The word boundaries word_sweep_db takes at width W: every one at the register-held widths
+    (the kernels' word loops are unrolled: each word has code of its own), and at the runtime
+    widths (loops over the words) the first two, both sides of word 64 (4,096 eids: the device
+    build's limit), the middle and the last."""
+    if W <= 64:
+        return list(range(1, W))
+    return sorted({1, 2, 63, 64, 65, W // 2 - 1, W // 2, W - 1})
+
+
+def sweep_case(W):
+    return _cached(("sweep", W), lambda: word_sweep_db(W, sweep_ks(W)))
 
 
 def big_row_cases():

@@ -96,7 +96,7 @@ def test_f2_cases_tight_and_row_lengths():
                for h in range(len(noise.hub_rows)))
 
 
-@pytest.mark.parametrize("w", [1, 2])
+@pytest.mark.parametrize("w", [1, 2, 4, 8])
 def test_lattice_cases_tight_and_placed(w):
     rg = E.wave_ranges()
     assert all(v > 0 and v % 64 == 0 for v in rg.values())
@@ -104,6 +104,12 @@ def test_lattice_cases_tight_and_placed(w):
     for name, db, level, claim in E.lattice_cases(w):
         assert E.mask_width(db) == w, name
         E.check_lattice_claim(db, level, claim)
+        if w > 2:  # stretched hubs: exactly 64 w itemsets, the hub's own from right behind the prefix to the last
+            for h, r in enumerate(db.hub_rows):
+                sets, own = E.itemsets_of(db.rows[r]), set(db.hub_items[h])
+                at = [k for k, s in enumerate(sets) if own & set(s)]
+                assert len(sets) == 64 * w and at[0] == 2 and at[-1] == 64 * w - 1, name
+                assert {k >> 6 for k in at} == set(range(w)), name
         if "start" in claim:
             starts[level].add(claim["start"])
         if name == "lengths" or name.endswith(("start64", "start511", "start512")) or name == "hub-last":
@@ -167,6 +173,74 @@ def test_mask_and_big_row_cases_tight():
             assert psup(db, p) == 2
         for x, y in db.rest_pairs:
             assert psup(db, E.planted_relation(db, x, y)) == 1
+
+
+# ------------------------------------------------------------ word sweep
+SWEEP_LABELS = {"G1a", "G1b", "G1c", "G2a", "G2b", "G3", "G4", "G5a", "G5b", "G6a", "G6b", "G7", "G8", "G9a", "G9b"}
+
+
+def assert_sweep_tight(db, frequent):
+    """Every t2 decision at exactly 2, every t1 decision at exactly 1, re-counted by definition;
+    both prefix-class parents of every decision frequent at exactly 2 (`frequent`: the oracle's
+    mine as a dict)."""
+    assert db.t2 and db.t1 and not set(db.t2) & set(db.t1)
+    for want, pats in ((2, db.t2), (1, db.t1)):
+        for p in pats:
+            assert psup(db, p) == want, (db.name, db.boundary[p], db.gadget[p], p)
+            assert (p in frequent) == (want == 2)
+            for parent in E.prefix_parents(p):
+                assert frequent.get(parent) == 2, (db.name, db.boundary[p], db.gadget[p], parent)
+
+
+@pytest.mark.parametrize("W,Ee,ks", [(2, 70, None), (2, 128, None), (4, 256, (1, 3)), (4, 200, (2, 3))], ids=str)
+def test_word_sweep_small_vs_brute(W, Ee, ks):
+    db = E.word_sweep_db(W, ks, Ee)
+    o = oracle.spade(db.records(), db.support)
+    assert o["minsup"] == 2 and E.mask_width(db) == W
+    assert o["patterns"] == brute.brute_spade(db.records(), db.support) == db.expected()
+    assert_sweep_tight(db, dict(o["patterns"]))
+    # S ends right after the boundary: the gadgets that need eid b + 2 are left out, the rest stays
+    if Ee == 70:
+        assert {db.gadget[p] for p in db.t2 + db.t1} == SWEEP_LABELS - {"G8"}
+        cut = E.word_sweep_db(2, E=65)
+        assert {cut.gadget[p] for p in cut.t2 + cut.t1} == SWEEP_LABELS - {"G4", "G5b", "G6b", "G7", "G8"}
+        assert_sweep_tight(cut, dict(oracle.spade(cut.records(), cut.support)["patterns"]))
+
+
+@pytest.mark.parametrize("W", E.SWEEP_W)
+def test_word_sweep_cases_tight_and_placed(W):
+    """The DBs of test_mask_word_sweep: the mask width, the boundaries each case claims (every
+    one at the register-held widths; 1, 2, 63, 64, 65, W / 2 - 1, W / 2 and W - 1 at the runtime
+    widths), every gadget at every boundary, every decision exactly on its threshold through
+    tight parents, and the generator's closed form equal to the oracle's mine."""
+    db = E.sweep_case(W)
+    assert E.mask_width(db) == W == db.W and db.E == 64 * W
+    assert len([s for s in E.itemsets_of(db.rows[0]) if s]) == 64 * W
+    want = set(range(1, W)) if W <= 64 else {1, 2, 63, 64, 65, W // 2 - 1, W // 2, W - 1}
+    assert set(db.ks) == want == set(db.boundary.values())
+    for k in want:
+        labels = {db.gadget[p] for p in db.t2 + db.t1 if db.boundary[p] == k}
+        assert labels == SWEEP_LABELS - ({"G8"} if k == W - 1 else set()), (W, k)
+    o = oracle.spade_tokens(db.seq_off, db.tokens, db.support)
+    assert o["minsup"] == 2 and o["patterns"] == db.expected()
+    assert_sweep_tight(db, dict(o["patterns"]))
+    # the eids the gadgets are named after: a decision of boundary k has an item on eid 64 k - 1 or 64 k
+    for p, k in db.boundary.items():
+        es = {e for s in p for it in s for e in db.eids[it]}
+        assert es & {64 * k - 1, 64 * k} and max(es) <= 64 * (k + 1), (W, k, db.gadget[p])
+
+
+def test_word_sweep_off_threshold_is_noticed():
+    """A second private sequence for one gadget moves its decision off the threshold: the
+    tightness assertions trip."""
+    db = E.word_sweep_db(2)
+    moved = E.EdgeDB(db.rows + [db.rows[1 + len(db.t2)]])
+    moved.t2, moved.t1, moved.boundary, moved.gadget, moved.name = db.t2, db.t1, db.boundary, db.gadget, "moved"
+    o = oracle.spade_tokens(moved.seq_off, moved.tokens, 1.5 / len(moved.rows))
+    assert o["minsup"] == 2
+    with pytest.raises(AssertionError):
+        assert_sweep_tight(moved, dict(o["patterns"]))
+    assert psup(moved, db.t1[0]) == 2
 
 
 def test_tsr_long_cases_tight():

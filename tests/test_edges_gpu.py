@@ -4,7 +4,8 @@ The DBs come from tests/edge_dbs.py: every candidate counter sits exactly at
 minsup or exactly one below, so a count, emit or F2 kernel that is off by one
 anywhere changes the frequent set; and each DB is placed on a constant the
 kernels branch on (row and run lengths 63 / 64 / 65, run starts around the
-wave ranges, tile and mode-switch row counts, mask widths up to 1,024 words,
+wave ranges, tile and mode-switch row counts, mask widths up to 1,024 words
+and every word boundary of a mask,
 TSR rows longer than one chunk, deciding sids on word and group boundaries).
 tests/test_edge_dbs.py proves those claims on the same objects without a GPU.
 
@@ -128,17 +129,19 @@ def test_root_f2_row_lengths(eng, env, monkeypatch):
 
 # ------------------------------------------------------------ 2. lattice windows
 LATTICE_ENVS = ["", "FSM_COUNT_PATH=keys", "FSM_COUNT_PATH=atomic FSM_COUNT_KERNEL=thread", "FSM_EMIT_PATH=chunk",
-                "FSM_EMIT_CAP=17"]
+                "FSM_EMIT_CAP=17", "FSM_COUNT_PATH=sparse"]
 
 
 @pytest.mark.parametrize("env", LATTICE_ENVS, ids=lambda e: e.replace(" ", ",") or "default")
-@pytest.mark.parametrize("w", [1, 2])
+@pytest.mark.parametrize("w", [1, 2, 4, 8])
 def test_lattice_windows(eng, w, env, monkeypatch):
     """Runs of 63..66 entries and of 127..257 (the long-run list) in [A1] and
     [A1 -> A2]; a 64-entry run starting 63 before, one before and on every
     multiple of 64 up to 512 (the wave ranges of k_emit2: root 128, W = 1
     lattice 192, W > 1 lattice 64, and of k_count2: 256) in [A1] and in the
-    root; a hub that is the last run (it ends at E).  W = 1 and W = 2."""
+    root; a hub that is the last run (it ends at E).  W = 1, 2, and 4 and 8 (the
+    other two instantiations of k_emit2 / k_count2), where every hub is stretched
+    over the whole mask: its entries' bits lie in every word."""
     setenv(monkeypatch, env)
     for name, db, level, claim in E.lattice_cases(w):
         E._cached(("latgeo", w, name), lambda: E.check_lattice_claim(db, level, claim) and True)
@@ -198,6 +201,60 @@ def test_mask_widths(eng, E_W):
     st = check_spade(eng, db)
     assert st["mask_words"] == W
     assert st["k0_device"] == (1 if Ee <= 4096 else 0)
+
+
+SWEEP_ENVS = ["", "FSM_EMIT_PATH=chunk", "FSM_COUNT_PATH=atomic FSM_COUNT_KERNEL=thread", "FSM_COUNT_PATH=keys",
+              "FSM_COUNT_PATH=sparse", "FSM_ROOT_DB=0", "FSM_EMIT_CAP=0"]
+# k_emit2, k_count2 and the DB-direct root exist at W = 1, 2, 4, 8: from 16 words on FSM_EMIT_PATH=chunk and
+# FSM_ROOT_DB=0 select what the default runs already (FSM_COUNT_PATH=atomic still forces the count path)
+SWEEP_CASES = [(W, env) for W in E.SWEEP_W for env in SWEEP_ENVS
+               if W <= 8 or env not in ("FSM_EMIT_PATH=chunk", "FSM_ROOT_DB=0")]
+
+
+def check_sweep(eng, db, text):
+    """check_spade; a failure names the word boundaries (and gadgets) of the differing patterns."""
+    o = spade_ref(db)
+    try:
+        return check_spade(eng, db, text=text)
+    except AssertionError as err:
+        pats, _, _ = gpu_spade(eng, db, text)
+        got, exp = dict(pats), dict(o["patterns"])
+        diff = [p for p in set(got) | set(exp) if got.get(p) != exp.get(p)]
+        raise AssertionError("%s: (word boundary, gadget) of the %d differing patterns: %r; %s"
+                             % (db.name, len(diff), db.words_of(diff), err)) from None
+
+
+@pytest.mark.parametrize("W,env", SWEEP_CASES, ids=lambda x: x if isinstance(x, int) else x.replace(" ", ",") or "default")
+def test_mask_word_sweep(eng, W, env, monkeypatch):
+    """One decision (support exactly 2 or exactly 1) on every word boundary of the mask at the
+    register-held widths 2 .. 64, and on boundaries 1, 2, 63, 64, 65, W / 2 - 1, W / 2, W - 1 at
+    the runtime widths 128 .. 1,024 (edge_dbs.word_sweep_db): temporal and equality counts whose
+    deciding bit is the first of word k, temporal children cleared up to the last bit of word
+    k - 1 or the first of word k whose new lo lies in word k or k + 1, children of equality
+    joins, and joins that read those children's masks and lo / hi.  Token path and text path."""
+    setenv(monkeypatch, env)
+    db = E.sweep_case(W)
+    for text in (False, True):
+        st = check_sweep(eng, db, text)
+        assert st["mask_words"] == W
+        if not text:  # the device build takes rows of up to 8,192 tokens and 4,096 eids: S at W = 64 is longer
+            assert st["k0_device"] == (1 if db.E <= 4096 and len(db.rows[0]) <= 8192 else 0)
+
+
+@pytest.mark.parametrize("W", E.SWEEP_W)
+def test_mask_word_sweep_supports(eng, W):
+    """k_ps_count on the same words: the support of every decision of the sweep, given as a
+    pattern, is 2 where S holds it and 1 where it does not."""
+    from spark_fsm_amd import MODE_SPADE
+    db = E.sweep_case(W)
+    h = eng.db_from_tokens(db.sids, db.seq_off, db.tokens, MODE_SPADE)
+    try:
+        got = eng.pattern_supports(h, db.t2 + db.t1).tolist()
+    finally:
+        h.free()
+    want = [2] * len(db.t2) + [1] * len(db.t1)
+    bad = [(db.boundary[p], db.gadget[p], g, w) for p, g, w in zip(db.t2 + db.t1, got, want) if g != w]
+    assert not bad, "W = %d: (word boundary, gadget, GPU, expected): %r" % (W, bad[:8])
 
 
 # ------------------------------------------------------------ 5. a DB row of 65,535 / 65,536 entries
