@@ -16,7 +16,10 @@ itemsets), `word_sweep_db` (one decision on every word boundary of the mask),
 and `k0_image`, the DB image by definition from the token rules (SPADE.scala:53-106, :151-210; TSR.scala:52-94, :109-143); and the TSR
 families placed on the expansion kernels' constants (`tsr_constants`, read
 from tsr_engine.hip): `tsr_probe_edges`, `tsr_kid_edges`, `tsr_chain`,
-`tsr_pair_edges`.
+`tsr_pair_edges`; and `tall_spade`, SPADE along the sequence axis: R short rows mined at a
+minsup in the thousands, the supporting rows placed on the root F2's row blocks
+(`spade_constants`, `f2_row_blocks`, read from spade_engine.hip), with the K0 cases
+of the same sizes (`k0_stage_case`, `k0_extreme_cases`, `with_lead`).
 """
 import os
 import random
@@ -1280,3 +1283,366 @@ def pair_phase_threshold(rules, k):
 
 def tsr_pair_case():
     return _cached("tsr_pair", lambda: tsr_pair_edges(600))
+
+
+# ---------------------------------------------------------------- SPADE along the sequence axis
+K0_SRC = os.path.join(ROOT, "spark-fsm_amd", "csrc", "k0_build.hip")
+UTIL_SRC = os.path.join(ROOT, "spark-fsm_amd", "csrc", "device_util.hip")
+
+
+def spade_constants():
+    """The constants of spade_engine.hip (and the scan tile of device_util.hip) the tall DBs are
+    placed on, read from the source itself (every one must be found): kF2MaxRows, kF2MaxBlocks,
+    kChunk, the default of FSM_F2_BLOCKS and the lower bound of rpb in Miner::f2_geometry, and
+    kScanTile = kScanT * kScanV."""
+    def make():
+        with open(ENGINE_SRC) as f:
+            src = f.read()
+        out = {}
+        for name in ("kF2MaxRows", "kF2MaxBlocks", "kChunk"):
+            m = re.search(r"^constexpr\s+uint32_t\s+%s\s*=\s*(\d+)\s*;" % name, src, re.M)
+            assert m, "no constexpr %s in spade_engine.hip" % name
+            out[name] = int(m.group(1))
+        m = re.search(r'clamped\("FSM_F2_BLOCKS",\s*1,\s*kF2MaxBlocks,\s*(\d+)\)', src)
+        assert m, "no default of FSM_F2_BLOCKS in spade_engine.hip"
+        out["f2_blocks"] = int(m.group(1))
+        m = re.search(r"g\.rpb\s*=\s*std::min<uint32_t>\(kF2MaxRows,\s*std::max<uint32_t>\((\d+)u,\s*"
+                      r"\(g\.R \+ nb_want - 1\) / nb_want\)\);", src)
+        assert m, "Miner::f2_geometry no longer derives rpb as min(kF2MaxRows, max(16, ceil(R / blocks)))"
+        out["rpb_min"] = int(m.group(1))
+        assert re.search(r"g\.nblk\s*=\s*\(g\.R \+ g\.rpb - 1\) / g\.rpb;", src), "nblk is no longer ceil(R / rpb)"
+        with open(UTIL_SRC) as f:
+            util = f.read()
+        t = re.search(r"^constexpr\s+int\s+kScanT\s*=\s*(\d+)\s*;", util, re.M)
+        v = re.search(r"^constexpr\s+int\s+kScanV\s*=\s*(\d+)\s*;", util, re.M)
+        assert t and v and re.search(r"kScanTile\s*=\s*kScanT\s*\*\s*kScanV\s*;", util), "no kScanTile in device_util.hip"
+        out["kScanTile"] = int(t.group(1)) * int(v.group(1))
+        return out
+    return dict(_cached("spade_constants", make))
+
+
+def f2_row_blocks(R, f2_blocks=None):
+    """(rpb, nblk) of the root F2 as Miner::f2_geometry derives them for R rows under
+    FSM_F2_BLOCKS = f2_blocks (None: the default), or None where the group path does not apply
+    (more rows than kF2MaxBlocks blocks of rpb rows cover)."""
+    c = spade_constants()
+    want = min(c["f2_blocks"] if f2_blocks is None else f2_blocks, c["kF2MaxBlocks"])
+    rpb = min(c["kF2MaxRows"], max(c["rpb_min"], -(-R // want)))
+    if rpb * c["kF2MaxBlocks"] < R:
+        return None
+    return rpb, -(-R // rpb)
+
+
+def policy_name(pol):
+    return pol[0] if len(pol) == 1 else "%s(%d)" % pol
+
+
+def tall_policy_rows(R, pol):
+    """(critical rows, critical row c) of a policy whose rows do not depend on S, or None where
+    the policy has no row at this R (edges and lone need a second block).  Blocks are the B rows
+    [k B, (k + 1) B), the last one partial."""
+    kind = pol[0]
+    if kind == "dense":
+        return list(range(R)), R - 1
+    if kind in ("head", "tail"):
+        return [], 0 if kind == "head" else R - 1
+    B = pol[1]
+    nb = -(-R // B)
+    if kind == "every":
+        rows = {0, R - 1}
+        for k in range(nb):
+            rows.add(min(R, (k + 1) * B) - 1 if k % 2 else k * B)
+        return sorted(rows), R - 1
+    if nb < 2:
+        return None
+    if kind == "edges":
+        return sorted({r for k in range(1, nb) for r in (k * B - 1, k * B)}), (nb - 1) * B
+    assert kind == "lone"
+    first = (nb - 1) * B
+    c = first + (R - first) // 2
+    return [c], c
+
+
+TALL_MIN_S = 8
+# the slots (itemsets after the prefix) of a placement's gadgets, in the two layouts a placement's
+# rows alternate between: the gadgets in this order, and in the reverse order
+_TALL_ORDER = (("F", 1), ("T+", 2), ("T-", 2), ("E+", 1), ("E-", 1), ("C+", 3), ("C-", 3))
+TALL_SLOTS = sum(n for _, n in _TALL_ORDER)
+TALL_ITEMS = 16
+
+
+def _tall_slot_maps():
+    maps = []
+    for order in (_TALL_ORDER, _TALL_ORDER[::-1]):
+        at, s = {}, 0
+        for g, n in order:
+            at[g] = s
+            s += n
+        maps.append(at)
+    return maps
+
+
+class TallSpade(EdgeDB):
+    """tall_spade's result.
+    S            the minsup the DB is mined at; `support` the relative support that gives it
+    placements   {policy label: sorted rows of P}, crit {policy label: critical row c}
+    items        {policy label: {"f", "g", "x", "y", "u", "v", "p", "q", "p2", "q2", "cx", "cy", "cz", "dx",
+                 "dy", "dz": item}}: F1+ f, F1- g, T+ x -> y, T- u -> v, E+ (p q), E- (p2 q2),
+                 C+ cx -> cy -> cz, C- dx -> dy -> dz
+    t2, t1       the decisions of support exactly S / exactly S - 1; policy_of, gadget {decision: label}
+    member       per row: the number of placements it belongs to"""
+
+    @property
+    def support(self):
+        return 1.0 if self.S == len(self.rows) else (self.S - 0.5) / len(self.rows)
+
+    def where(self, p):
+        pol = self.policy_of[p]
+        return "R = %d, policy %s, critical row %d, gadget %s" % (len(self.rows), pol, self.crit[pol], self.gadget[p])
+
+    def root_entries(self):
+        """(frequent item, sequence) entries of the root class: every item but the F1- ones."""
+        rare = {it["g"] for it in self.items.values()}
+        return int(np.count_nonzero((self.tokens >= 0) & ~np.isin(self.tokens, list(rare))))
+
+
+def tall_spade(R, S, policies, prefix=1, seed=1):
+    """R short sequences mined at minsup S (None: the most rows any policy needs, at least
+    TALL_MIN_S).  Every row starts with the one-item itemsets A1 .. Ad (d = prefix, items 1 .. d), so
+    every row holds a frequent entry and R is the engine's row count.
+
+    For each policy (tall_policy_rows; head is rows 0 .. S - 1, tail R - S .. R - 1) a placement P
+    of exactly S rows: the policy's critical rows, padded with seeded-random others (rows that are
+    critical to no policy first; for `lone`, rows outside the last block), and ONE critical row c
+    in P.  Sixteen fresh items per placement, each in no row outside P, plant the gadgets:
+
+    F1+  f in every row of P                                   support S
+    F1-  g in P without c                                      S - 1
+    T+   x -> y in every row                                   S
+    T-   u -> v in P without c, v -> u in c                    u, v: S; u -> v: S - 1
+    E+   (p q) in every row                                    S
+    E-   (p2 q2) in P without c; in c p2 and q2 in neighbouring itemsets      p2, q2: S; (p2 q2): S - 1
+    C+   cx -> cy -> cz in every row                           S, through the parents cx -> cy and cx -> cz at S
+    C-   dx -> dy -> dz in P without c, dx -> dz -> dy in c    dx -> dy, dx -> dz: S; the chain: S - 1
+
+    A lost increment at c, or anywhere in P, turns an S into S - 1; a repeated one an S - 1 into S.
+    With the prefix every decision repeats behind every sub-chain of A1 .. Ad (one and two classes
+    down).  The gadgets of a placement take TALL_SLOTS itemsets in a fixed order in the even rows
+    of P and in the reverse order in the odd ones, so a pattern over two gadgets holds in about
+    half of P and stays below S; a row of several placements merges their itemsets slot by slot
+    (two placements share fewer than S rows).  A row of m placements has at most
+    16 m + TALL_SLOTS + 2 d + 1 tokens: at most 64 for m <= 2 (and for m = 3 with d = 1); the few
+    rows that more placements share are longer.  Rows of no placement hold the prefix alone."""
+    rng = random.Random(seed)
+    d = prefix
+    pols = []
+    for pol in policies:
+        got = tall_policy_rows(R, pol)
+        if got is not None:
+            pols.append((policy_name(pol), pol, got[0], got[1]))
+    if S is None:
+        S = max([TALL_MIN_S] + [len(rows) for _, _, rows, _ in pols])
+    assert 2 <= S <= R and all(len(rows) <= S for _, _, rows, _ in pols)
+    in_crit = set(r for _, _, rows, _ in pols for r in rows)
+    placements, crit = {}, {}
+    for label, pol, rows, c in pols:
+        if pol[0] == "head":
+            rows = list(range(S))
+        elif pol[0] == "tail":
+            rows = list(range(R - S, R))
+        have = set(rows)
+        if len(rows) < S:
+            limit = (-(-R // pol[1]) - 1) * pol[1] if pol[0] == "lone" else R
+            cand = [r for r in range(limit) if r not in have]
+            rng.shuffle(cand)
+            cand.sort(key=lambda r: r in in_crit)  # stable: rows critical to no policy first
+            rows = rows + cand[:S - len(rows)]
+        assert len(set(rows)) == S and c in rows, label
+        placements[label], crit[label] = sorted(rows), c
+    assert len({tuple(p) for p in placements.values()}) == len(placements), "two policies with the same placement"
+
+    maps = _tall_slot_maps()
+    slots = {}  # row -> TALL_SLOTS item lists
+    items, member = {}, np.zeros(R, dtype=np.int32)
+    t2, t1, policy_of, gadget = [], [], {}, {}
+    chains = [tuple((a,) for a in range(1, d + 1) if bits >> (a - 1) & 1) for bits in range(1 << d)]
+    for j, (label, P) in enumerate(placements.items()):
+        base = d + 1 + TALL_ITEMS * j
+        names = ("f", "g", "x", "y", "u", "v", "p", "q", "p2", "q2", "cx", "cy", "cz", "dx", "dy", "dz")
+        it = items[label] = {n: base + k for k, n in enumerate(names)}
+        c = crit[label]
+        for k, r in enumerate(P):
+            at = maps[k & 1]
+            sl = slots.setdefault(r, [[] for _ in range(TALL_SLOTS)])
+            member[r] += 1
+            isc = r == c
+
+            def put(g, off, name):
+                sl[at[g] + off].append(it[name])
+            put("F", 0, "f")
+            if not isc:
+                put("F", 0, "g")
+            put("T+", 0, "x"), put("T+", 1, "y")
+            put("T-", 1 if isc else 0, "u"), put("T-", 0 if isc else 1, "v")
+            put("E+", 0, "p"), put("E+", 0, "q")
+            put("E-", 0, "p2")
+            if isc:  # the itemset behind E-'s own: the next gadget's first, or one of this row's own
+                nxt = at["E-"] + 1
+                assert nxt < TALL_SLOTS
+                sl[nxt].append(it["q2"])
+            else:
+                put("E-", 0, "q2")
+            put("C+", 0, "cx"), put("C+", 1, "cy"), put("C+", 2, "cz")
+            put("C-", 0, "dx"), put("C-", 2 if isc else 1, "dy"), put("C-", 1 if isc else 2, "dz")
+        hold = [("F1+", ((it["f"],),)), ("T+", ((it["x"],), (it["y"],))), ("E+", ((it["p"], it["q"]),)),
+                ("C+", ((it["cx"],), (it["cy"],), (it["cz"],))),
+                ("C+ parent", ((it["cx"],), (it["cy"],))), ("C+ parent", ((it["cx"],), (it["cz"],))),
+                ("C- parent", ((it["dx"],), (it["dy"],))), ("C- parent", ((it["dx"],), (it["dz"],)))]
+        hold += [("%s item" % g, ((it[n],),)) for g, n in (("T-", "u"), ("T-", "v"), ("E-", "p2"), ("E-", "q2"))]
+        fail = [("F1-", ((it["g"],),)), ("T-", ((it["u"],), (it["v"],))), ("E-", ((it["p2"], it["q2"]),)),
+                ("C-", ((it["dx"],), (it["dy"],), (it["dz"],)))]
+        for ch in chains:
+            for lst, dec in ((t2, hold), (t1, fail)):
+                for g, p in dec:
+                    q = ch + p
+                    lst.append(q)
+                    policy_of[q], gadget[q] = label, g if not ch else "%s behind %d prefix item(s)" % (g, len(ch))
+    pre = [t for a in range(1, d + 1) for t in (a, -1)]
+    plain = pre + [-2]
+    rows = [plain] * R
+    for r, sl in slots.items():
+        rows[r] = pre + _row([sorted(s) for s in sl if s])
+    db = TallSpade(rows, "tall-R%d-S%d-%s" % (R, S, "+".join(placements)))
+    db.S, db.R, db.prefix_items, db.placements, db.crit, db.items = S, R, list(range(1, d + 1)), placements, crit, items
+    db.t2, db.t1, db.policy_of, db.gadget, db.member = t2, t1, policy_of, gadget, member
+    return db
+
+
+# FSM_F2_BLOCKS (None: the default) and the R of each tall DB; TALL_GEOMETRY is what the issue
+# states for them, asserted against f2_row_blocks in tests/test_edge_dbs.py
+TALL_R = ((None, (15, 16, 17)), (None, (16383, 16384, 16385)), (None, (65535, 65536, 65537)),
+          (1, (4095, 4096, 4097)), (2048, (32767, 32768, 32769)))
+TALL_GEOMETRY = {15: (16, 1), 16: (16, 1), 17: (16, 2), 16383: (16, 1024), 16384: (16, 1024), 16385: (17, 964),
+                 65535: (64, 1024), 65536: (64, 1024), 65537: (65, 1009), 4095: (4095, 1), 4096: (4096, 1),
+                 4097: (4096, 2), 32767: (16, 2048), 32768: (16, 2048), 32769: (17, 1928)}
+TALL_PREFIX2 = (16, 4097, 65536)  # these R carry two prefix items (decisions two classes down)
+TALL_MATRIX_R = (4097, 16385)
+TALL_NEAR_R = 65537
+
+
+def tall_blocks_env(R):
+    """The FSM_F2_BLOCKS a tall DB of R rows is placed for (None: the default)."""
+    return [b for b, rs in TALL_R if R in rs][0]
+
+
+def tall_env(R):
+    b = tall_blocks_env(R)
+    return "" if b is None else "FSM_F2_BLOCKS=%d" % b
+
+
+def tall_case(R, dense=False):
+    """The tall DB of R rows: every(B), edges(B), lone(B) for B = the root F2's rpb at this R and
+    its FSM_F2_BLOCKS and for B = 64 (the wave and tile sizes; without edges(64) where rpb divides
+    64), head and tail, all in one DB at the S the largest of them needs; dense: the DB with S = R, every row in P, c = R - 1."""
+    def make():
+        d = 2 if R in TALL_PREFIX2 else 1
+        if dense == "near":  # a minsup just below 2^16 under counts above it, three classes down
+            return tall_spade(R, R - 2, [("head",)], prefix=3, seed=R)
+        if dense:
+            return tall_spade(R, R, [("dense",)], prefix=d, seed=R)
+        rpb, _ = f2_row_blocks(R, tall_blocks_env(R))
+        pols = [(kind, rpb) for kind in ("every", "edges", "lone")]
+        if rpb != 64:  # where rpb divides 64 every row of edges(64) is a row of edges(rpb) already
+            pols += [(kind, 64) for kind in ("every", "edges", "lone") if kind != "edges" or 64 % rpb]
+        pols += [("head",), ("tail",)]
+        return tall_spade(R, None, pols, prefix=d, seed=R)
+    return _cached(("tall", R, dense), make)
+
+
+def tall_all_r():
+    return [R for _, rs in TALL_R for R in rs]
+
+
+# ---------------------------------------------------------------- K0 and the scan on the same sizes
+INT32_MAX, INT32_MIN = 2 ** 31 - 1, -2 ** 31
+K0_TALL_R = (4095, 4096, 4097, 32767, 32768, 32769)
+K0_STAGE_R = (524287, 524288, 524289)
+K0_STAGE_VARIANTS = ("last-max", "last-min", "first")
+K0_LEAD = (INT32_MAX, -1, 0, -1, 7)  # tokens before seq_off[0]: they belong to no row
+
+
+def k0_stage_constants():
+    """k0_build.hip's kStageBytes, kK0Wave, kK0Long, kK0Threads and the grid cap of k0_rows, read from the source."""
+    def make():
+        with open(K0_SRC) as f:
+            src = f.read()
+        out = {}
+        m = re.search(r"^constexpr\s+uint64_t\s+kStageBytes\s*=\s*uint64_t\((\d+)\)\s*<<\s*(\d+)\s*;", src, re.M)
+        assert m, "no kStageBytes in k0_build.hip"
+        out["kStageBytes"] = int(m.group(1)) << int(m.group(2))
+        for name in ("kK0Wave", "kK0Long", "kK0Threads"):
+            m = re.search(r"^constexpr\s+uint32_t\s+%s\s*=\s*(\d+)\s*;" % name, src, re.M)
+            assert m, "no %s in k0_build.hip" % name
+            out[name] = int(m.group(1))
+        m = re.search(r"grid_rows\s*=.*kK0Threads - 1\) / kK0Threads,\s*(\d+)\)\);", src)
+        assert m, "no grid cap of k0_rows in k0_build.hip"
+        out["rows_grid"] = int(m.group(1))
+        out["rows_lap"] = out["rows_grid"] * out["kK0Threads"] // 64  # waves (rows) per grid-stride lap
+        return out
+    return dict(_cached("k0_constants", make))
+
+
+def k0_extreme_cases():
+    """(name, rows, modes): item values within 2^20 of INT32_MAX and of INT32_MIN (the extremes
+    themselves included, and repeated within a row), on the wave path (a row of exactly 64 tokens
+    and 32 itemsets) and on the block path (a row of 8,192 tokens).  The sort key of an item is
+    value ^ 0x80000000 over its eid: for INT32_MAX its high word is all ones, as in the sentinel
+    key of a lane without an item.  Negative values are items in SPADE only."""
+    def make():
+        rng = random.Random(9)
+        out = []
+        for side, lo, hi, modes in (("max", INT32_MAX - 2 ** 20, INT32_MAX, ("spade", "tsr")),
+                                    ("min", INT32_MIN, INT32_MIN + 2 ** 20, ("spade",))):
+            ends = (lo, hi, hi - 1, lo + 1)
+            for path, sets in (("wave", 32), ("block", 4096)):
+                vals = [ends[k % 4] if k % 5 == 0 or k == sets - 1 else rng.randint(lo, hi) for k in range(sets)]
+                vals[-1] = hi if side == "max" else lo  # the extreme in the last itemset too
+                row = [t for v in vals for t in (v, -1)]
+                out.append(("int32-%s-%s" % (side, path), [row, [hi, -1, lo, -1], [lo, hi, -1, -2]], modes))
+        return out
+    return _cached("k0_extreme", make)
+
+
+def k0_stage_case(R, variant):
+    """R rows <x, -1> as token arrays (sids, seq_off, tokens), and their image in closed form (one
+    entry per row at eid / itemset 0; `mode` picks the fields).  The n + 1 offsets and the 2 R
+    tokens end on both sides of one staging chunk.  x is 100 + r % 1,000 except for the smallest
+    (7) and the largest (5,000) value: last-max / last-min put one of them in the last row alone
+    (the row of the last two tokens: at R = 524,289 a chunk of its own), `first` puts them in rows
+    0 and 1."""
+    x = 100 + np.arange(R, dtype=np.int64) % 1000
+    if variant == "last-max":
+        x[-1] = 5000
+    elif variant == "last-min":
+        x[-1] = 7
+    else:
+        assert variant == "first"
+        x[0], x[1] = 7, 5000
+    tokens = np.empty(2 * R, dtype=np.int64)
+    tokens[0::2], tokens[1::2] = x, -1
+    vals = np.unique(x)
+
+    def image(mode):
+        img = {"rows": R, "entries": R, "items": len(vals), "row_off": np.arange(R + 1, dtype=np.uint32),
+               "item": np.searchsorted(vals, x).astype(np.uint32), "item_val": vals.astype(np.int32)}
+        if mode == "spade":
+            img.update(mask_words=1, max_occ=1, mask=np.ones(R, dtype=np.uint64))
+        else:
+            img.update(first=np.zeros(R, dtype=np.uint32), last=np.zeros(R, dtype=np.uint32))
+        return img
+    return np.arange(R, dtype=np.int32), 2 * np.arange(R + 1, dtype=np.int64), tokens, image
+
+
+def with_lead(db, lead=K0_LEAD):
+    """(seq_off, tokens) of a DB with `lead` tokens in front that belong to no row: seq_off[0] = len(lead)."""
+    return db.seq_off + len(lead), np.concatenate([np.array(lead, dtype=np.int64), db.tokens])

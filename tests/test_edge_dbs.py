@@ -8,6 +8,8 @@ the tightness claim itself, re-counted by definition (oracle.pattern_support /
 oracle.rule_support): every selected relation exactly at the threshold, a
 sample of the rest (first, last and middle ranks included) exactly one below;
 and the geometry each case is named after."""
+import math
+
 import numpy as np
 import pytest
 
@@ -550,3 +552,174 @@ def test_tsr_pair_case_placed():
     assert ids == {15, 16, 47, 48, 111, 112, 239, 240, 495, 496}
     for i in ids:
         assert {j - i for a, j in db.pairs if a == i} == {1, 63, 64, 65, db.U - 1 - i}
+
+
+# ------------------------------------------------------------ SPADE along the sequence axis
+def test_tall_geometry_table():
+    """rpb and nblk of the root F2 for every R of the tall DBs, as Miner::f2_geometry's formula
+    (its constants read from spade_engine.hip) gives them, against the stated table."""
+    c = E.spade_constants()
+    assert c["kF2MaxRows"] >= 64 and c["kF2MaxBlocks"] >= c["f2_blocks"] and c["rpb_min"] <= 64
+    assert sorted(E.TALL_GEOMETRY) == sorted(E.tall_all_r())
+    for blocks, rs in E.TALL_R:
+        for R in rs:
+            assert E.f2_row_blocks(R, blocks) == E.TALL_GEOMETRY[R], (blocks, R)
+    # what the families are named after: nblk reaches kF2MaxBlocks, rpb reaches kF2MaxRows, and at
+    # 4,097 rows in one target block the last block holds one row
+    assert E.f2_row_blocks(32768, 2048) == (16, c["kF2MaxBlocks"])
+    assert E.f2_row_blocks(4096, 1) == (c["kF2MaxRows"], 1) and 4097 - E.f2_row_blocks(4097, 1)[0] == 1
+    # the branch no case takes: more rows than kF2MaxBlocks blocks of kF2MaxRows rows
+    most = c["kF2MaxRows"] * c["kF2MaxBlocks"]
+    assert E.f2_row_blocks(most) == (c["kF2MaxRows"], c["kF2MaxBlocks"]) and E.f2_row_blocks(most + 1) is None
+    # the sizes also lie on both sides of a scan tile, and of one lap of k0_rows' waves
+    k0 = E.k0_stage_constants()
+    assert {c["kScanTile"] - 1, c["kScanTile"], c["kScanTile"] + 1} <= set(E.tall_all_r()) & set(E.K0_TALL_R)
+    assert {k0["rows_lap"] - 1, k0["rows_lap"], k0["rows_lap"] + 1} <= set(E.tall_all_r()) & set(E.K0_TALL_R)
+
+
+def _tall_policy_claims(db, R):
+    """Each placement's rows are the first / last / only rows of blocks that its policy names."""
+    rpb, nblk = E.f2_row_blocks(R, E.tall_blocks_env(R))
+    seen = set()
+    for label, P in db.placements.items():
+        Pset, c = set(P), db.crit[label]
+        assert len(P) == len(Pset) == db.S and c in Pset and 0 <= P[0] and P[-1] < R, label
+        kind = label.split("(")[0]
+        seen.add(label)
+        if kind == "dense":
+            assert P == list(range(R)) and c == R - 1
+            continue
+        if kind == "head":
+            assert P == list(range(db.S)) and c == 0
+            continue
+        if kind == "tail":
+            assert P == list(range(R - db.S, R)) and c == R - 1
+            continue
+        B = int(label.split("(")[1][:-1])
+        assert B in (rpb, 64), label
+        nb = -(-R // B)
+        last = range((nb - 1) * B, R)  # the last block, partial unless B divides R
+        if kind == "every":
+            assert {0, R - 1} <= Pset and c == R - 1, label
+            for k in range(nb):
+                first, end = k * B, min(R, (k + 1) * B) - 1
+                assert (end if k % 2 else first) in Pset, (label, k)
+        elif kind == "edges":
+            assert nb >= 2 and c == last[0], label
+            for k in range(1, nb):
+                assert k * B - 1 in Pset and k * B in Pset, (label, k)
+        else:
+            assert kind == "lone" and nb >= 2 and [r for r in P if r in last] == [c], label
+    return seen, rpb, nblk
+
+
+@pytest.mark.parametrize("dense", [False, True], ids=["placed", "dense"])
+@pytest.mark.parametrize("R", E.tall_all_r())
+def test_tall_spade_claims(R, dense):
+    """Every tall DB: the policies' geometry, every gadget item's support (S; the F1- item S - 1)
+    and rows (its placement and no other row), the row lengths, and the oracle's answer: minsup S,
+    every t2 decision at exactly S, no t1 decision; the t1 decisions hold in exactly S - 1 rows."""
+    db = E.tall_case(R, dense)
+    S = db.S
+    assert len(db.rows) == R and math.ceil(db.support * R) == S and (db.support == 1.0) == dense
+    seen, rpb, nblk = _tall_policy_claims(db, R)
+    if dense:
+        assert S == R and seen == {"dense"}
+    else:
+        want = {"every(%d)" % rpb, "every(64)", "head", "tail"}
+        if nblk >= 2:  # a second block: a first row of the last block, and a last block to be alone in
+            want |= {"edges(%d)" % rpb, "lone(%d)" % rpb}
+        assert want <= seen and S == max([E.TALL_MIN_S] + [
+            len(E.tall_policy_rows(R, (l.split("(")[0], int(l.split("(")[1][:-1])))[0]) for l in seen if "(" in l])
+        assert S > 100 or R <= 17
+        # the last row of a partial last block / the only row of a block supports a decision
+        assert R - 1 in db.placements["every(%d)" % rpb]
+    _tall_row_item_oracle_claims(db, R)
+
+
+def _tall_row_item_oracle_claims(db, R):
+    """The row lengths, every gadget item's rows, and the oracle's answer on every decision; returns that answer."""
+    S = db.S
+    d = len(db.prefix_items)
+    lens = np.diff(db.seq_off)
+    seq_of = np.repeat(np.arange(R), lens)
+    assert all(r[:2 * d] == [t for a in db.prefix_items for t in (a, -1)] for r in db.rows[:64] + db.rows[-64:])
+    assert np.all(lens <= 16 * db.member + np.where(db.member > 0, E.TALL_SLOTS, 0) + 2 * d + 1)
+    assert np.all(lens[db.member <= 2] <= 64) and (R <= 17 or np.count_nonzero(lens > 64) <= R // 50) and lens.max() <= 128
+    for label, P in db.placements.items():
+        for name, it in db.items[label].items():
+            rows = seq_of[db.tokens == it]
+            want = [r for r in P if r != db.crit[label]] if name == "g" else P
+            assert rows.tolist() == want, (label, name)
+    o = oracle.spade_tokens(db.seq_off, db.tokens, db.support)
+    assert o["minsup"] == S
+    got = dict(o["patterns"])
+    for p in db.t2:
+        assert got.get(p) == S, db.where(p)
+    for p in db.t1:
+        assert p not in got, db.where(p)
+    assert len(set(db.t2 + db.t1)) == len(db.t2) + len(db.t1)
+    for p in db.t1[:: max(1, len(db.t1) // 16)]:
+        assert psup(db, p) == S - 1, db.where(p)
+    assert db.root_entries() == sum(s for p, s in o["patterns"] if len(p) == 1 and len(p[0]) == 1)
+    return got
+
+
+def test_tall_near_dense_claims():
+    """The near-dense DB: a minsup just below 2^16 under lattice counts above it.  65,537 rows, the
+    head placement of S = 65,535 rows, three prefix items: A1 -> A2 -> A3 (counted in a class, not by
+    the root F2) and every one of its sub-chains has support 65,537, the decisions 65,535 / 65,534."""
+    R = E.TALL_NEAR_R
+    db = E.tall_case(R, "near")
+    assert db.S == R - 2 == 2 ** 16 - 1 and math.ceil(db.support * R) == db.S and len(db.prefix_items) == 3
+    _tall_policy_claims(db, R)
+    got = _tall_row_item_oracle_claims(db, R)
+    for p in (((1,), (2,), (3,)), ((1,), (2,)), ((2,), (3,)), ((1,), (3,))):
+        assert got[p] == R > 2 ** 16
+
+
+@pytest.mark.parametrize("R", [15, 16, 17, 200])
+def test_tall_spade_small_vs_brute(R):
+    """At the smallest R, and at one of a few hundred rows, the oracle equals the definitional enumerator."""
+    if R == 200:
+        dbs = [E.tall_spade(200, None, [("every", 16), ("lone", 16), ("tail",)], prefix=1, seed=3),
+               E.tall_spade(200, 200, [("dense",)], prefix=2, seed=3)]
+    else:
+        dbs = [E.tall_case(R), E.tall_case(R, dense=True)]
+    for db in dbs:
+        o = oracle.spade_tokens(db.seq_off, db.tokens, db.support)
+        assert o["minsup"] == db.S
+        assert o["patterns"] == brute.brute_spade(db.records(), db.support), db.name
+
+
+# ------------------------------------------------------------ K0 on the same sizes
+def test_k0_stage_sizes_and_closed_form():
+    """The staging cases end on both sides of one chunk of offsets and of tokens, and their closed
+    form is the image by definition (checked at a size k0_image takes at once)."""
+    k0 = E.k0_stage_constants()
+    per_off, per_tok = k0["kStageBytes"] // 8, k0["kStageBytes"] // 4
+    assert [2 * R - per_tok for R in E.K0_STAGE_R] == [-2, 0, 2]         # tokens: the last chunk is one row
+    assert [R + 1 - per_off for R in E.K0_STAGE_R] == [0, 1, 2]          # offsets: exactly one chunk, then 1 and 2 more
+    for variant in E.K0_STAGE_VARIANTS:
+        sids, so, tok, image = E.k0_stage_case(2500, variant)
+        rows = [tok[so[r]:so[r + 1]].tolist() for r in range(2500)]
+        for mode in ("spade", "tsr"):
+            ref, img = E.k0_image(rows, mode), image(mode)
+            assert sorted(ref) == sorted(img)
+            for key, want in ref.items():
+                assert np.array_equal(np.asarray(img[key]).astype(np.int64), np.asarray(want).astype(np.int64)), (variant, mode, key)
+        lo, hi = int(tok[tok >= 0].min()), int(tok.max())
+        at = {"last-max": [(hi, 2499)], "last-min": [(lo, 2499)], "first": [(lo, 0), (hi, 1)]}[variant]
+        for v, r in at:
+            assert np.flatnonzero(tok == v).tolist() == [2 * r]
+
+
+def test_k0_extreme_cases():
+    k0 = E.k0_stage_constants()
+    for name, rows, modes in E.k0_extreme_cases():
+        vals = [t for r in rows for t in r if t not in (-1, -2)]
+        assert max(vals) - min(vals) == 2 ** 20 and all(E.INT32_MIN <= v <= E.INT32_MAX for v in vals)
+        assert (E.INT32_MAX in vals) == ("max" in name) and (E.INT32_MIN in vals) == ("min" in name)
+        assert len(rows[0]) == (k0["kK0Wave"] if "wave" in name else k0["kK0Long"])
+        assert rows[0][-2] in (E.INT32_MAX, E.INT32_MIN) and len(set(rows[0])) < len(rows[0]) // 2 + 1
+        assert ("tsr" in modes) == (min(vals) >= 0)

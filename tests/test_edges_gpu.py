@@ -67,17 +67,23 @@ def gpu_tsr(eng, db, k, minconf, text=False):
 _ORACLE = {}
 
 
-def spade_ref(db, closed=False):
+def spade_ref(db, closed=False, minsup=2):
     """The oracle's answer for a DB, computed once per session and left unchanged.  closed: the
     generator's closed form (edge_dbs.closed_form_ref) for the DBs of 8,192 and more frequent
-    items, which the oracle takes 3 to 12 s each to mine."""
+    items, which the oracle takes 3 to 12 s each to mine.  minsup: what the DB is mined at (the
+    tall DBs of edge_dbs.tall_spade state their own; they list decisions, not a closed form)."""
     if id(db) not in _ORACLE:
         from oracle import oracle
         if closed:
             o = E.closed_form_ref(db)
         else:
             o = oracle.spade_tokens(db.seq_off, db.tokens, db.support)
-        assert o["minsup"] == 2 and o["patterns"] == db.expected(), db.name  # the closed form agrees
+        assert o["minsup"] == minsup, db.name
+        if isinstance(db, E.TallSpade):
+            got = dict(o["patterns"])
+            assert all(got.get(p) == db.S for p in db.t2) and not any(p in got for p in db.t1), db.name
+        else:
+            assert o["patterns"] == db.expected(), db.name  # the closed form agrees
         _ORACLE[id(db)] = (db, o)
     return _ORACLE[id(db)][1]
 
@@ -90,10 +96,10 @@ def tsr_ref(db, k, minconf):
     return _ORACLE[key][1]
 
 
-def check_spade(eng, db, text=False, closed=False, root=True):
-    o = spade_ref(db, closed)
+def check_spade(eng, db, text=False, closed=False, root=True, minsup=2):
+    o = spade_ref(db, closed, minsup)
     pats, meta, st = gpu_spade(eng, db, text)
-    assert meta["minsup"] == 2, db.name
+    assert meta["minsup"] == minsup, db.name
     if pats != o["patterns"]:
         got, exp = dict(pats), dict(o["patterns"])
         diff = [(p, got.get(p), exp.get(p)) for p in sorted(set(got) | set(exp)) if got.get(p) != exp.get(p)]
