@@ -138,6 +138,42 @@ constexpr size_t kHugeBlock = size_t(2) << 20;
 void* big_take(size_t bytes);
 void big_give(void* p);
 
+// malloc'd array without value-initialisation, released to the caller (freed by
+// fsm_patterns_free / fsm_rules_free)
+template <class T> struct MallocArr {
+    T* p = nullptr;
+    size_t n = 0;
+    MallocArr() = default;
+    explicit MallocArr(size_t n_) { alloc(n_); }
+    void alloc(size_t n_) {
+        big_give(p);
+        p = nullptr;
+        n = n_;
+        // large result arrays: big host blocks (2 MiB aligned, transparent huge pages, the
+        // largest reused from earlier mines: a dense mine's CSR is hundreds of MB of pages);
+        // fsm_patterns_free / fsm_rules_free hand them back through big_give
+        const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
+        if (bytes >= 4 * kHugeBlock) p = static_cast<T*>(big_take((bytes + kHugeBlock - 1) & ~(kHugeBlock - 1)));
+        else p = static_cast<T*>(std::malloc(bytes));
+        if (!p) throw Error(FSM_ENOMEM, "malloc failed");
+    }
+    MallocArr(const MallocArr&) = delete;
+    MallocArr& operator=(const MallocArr&) = delete;
+    ~MallocArr() { big_give(p); }
+    T& operator[](size_t i) { return p[i]; }
+    T* release() {
+        T* r = p;
+        p = nullptr;
+        return r;
+    }
+};
+
+template <class T> void copy_out(T*& dst, const std::vector<T>& src) {
+    dst = static_cast<T*>(std::malloc(std::max<size_t>(src.size(), 1) * sizeof(T)));
+    if (!dst) throw Error(FSM_ENOMEM, "malloc failed");
+    if (!src.empty()) std::memcpy(dst, src.data(), src.size() * sizeof(T));
+}
+
 // Mapped pinned host memory (kernels write results straight into it; the host
 // reads them after a stream sync, with no copy launch).
 struct PinnedBuf {

@@ -10,24 +10,49 @@
 // The counts are computed on the GPU; the order-dependent top-k bookkeeping
 // (save / registerAsCandidate / popMaximum with the rising minsup) is replayed
 // on the host in exactly the reference's order, so the result is bit-identical
-// to the CPU restatement whatever the GPU scheduling:
+// to the CPU restatement whatever the GPU scheduling.
+//
+// Kernels, in the order a mine launches them:
+//   DB finish    (once per DB, tsr_finish) k_vcount + scan + k_vscatter: the vertical
+//                lists; k_bitmap_build: one sid bitmap per item, NW words each, when
+//                they fit a quarter of the free HBM.
 //   pair phase   k_pairs: for a block of items i, every s in sids(i) scans the
 //                tail of row s (items j > i) and counts i=>j (first_i < last_j)
 //                and j=>i (first_j < last_i) into a dense block x U matrix;
-//                k_pairs_compact (wave ballot) emits the pairs that can reach
-//                the block's starting minsup, in (i, j) order.
-//   expansions   k_expand: one thread per sid of the rarest item of the rule;
+//                k_pairs_compact (wave ballot; count pass, scan, write pass) emits
+//                the pairs that can reach the block's starting minsup, in (i, j)
+//                order.  Sharded: each rank counts its own sequences, the candidate
+//                keys are united and k_pairs_gather reads every rank's partials.
+//   kept rows    the rows restricted to the K items that can still be in a rule
+//                (count pass, scan, k_off32, fill pass).  Bitmap path: k_rows_pack
+//                (entries packed as kid | first | last), then k_rank_dir and k_vfl
+//                (the kept items' rank directories and vertical entries).  List
+//                path: k_rows_keep (item / first / last / support, SoA).
+//   expansions   a launch expands up to B rules, one slot each, on one of the launch
+//                sets' streams.
+//     bitmap path (the default: bitmaps built, K <= kMaxKids, itemset indexes < 2^16)
+//                k_alive: kid codes when minsup rose.  k_exp_domain: a slot's domain
+//                sids, the AND of its items' bitmaps or its rarest item's list probed
+//                in the others; skipped for slots whose domain is their parent's kept
+//                rows in the arena.  k_exp_rows: firstX / lastY per domain row,
+//                the expandL / expandR candidates histogrammed in LDS passes into
+//                per-block partial rows; keeps the rows where the rule holds for
+//                its children.  k_expand_reduce: sums the partial rows, writes the
+//                records, queues the |sids(X u {c})| work the memo does not hold.
+//                k_dl: those counts (bitmap ANDs or list probes) and the headers.
+//     list path  k_expand: one wave per sid of the rarest item of the rule;
 //                binary-searches the rule's items in the row, derives firstX /
 //                lastY, and histograms the expandL (c before lastY) / expandR
-//                (c after firstX) candidates plus |sids(X u {c})|;
-//                k_expand_compact pulls the candidates with count >= minsup and
-//                re-zeroes the histograms.
+//                (c after firstX) candidates plus |sids(X u {c})| in per-slot HBM
+//                arrays; k_expand_collect pulls the touched candidates and re-zeroes
+//                the histograms; k_publish writes the headers.
+// The host side (below the kernels): TsrKnobs lists the environment switches, TsrMiner
+// holds one mine's state, tsr_mine lists its stages.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <deque>
-#include <functional>
 #include <memory>
 #include <queue>
 #include <set>
@@ -56,19 +81,9 @@ constexpr int kDlUnroll = 8;        // k_dl: independent words / sids per thread
 constexpr int kSpecDepth = 6;       // child speculation: levels per launch
 constexpr int kSpecMax = 2;         // child speculation: rules per level, in batches (2 x B)
 constexpr int kExpSets = 2;         // launch sets (buffers, stream, events) in flight
-// FSM_TSR_GRID="expand,collect,dl" overrides the per-launch grids (tuning sweeps)
+// the per-launch grids (TsrKnobs: FSM_TSR_GRID)
 struct TsrGrid {
     unsigned expand = kExpandBlocks, collect = kCollectBlocks, dl = kDlBlocks;
-    TsrGrid() {
-        if (const char* v = std::getenv("FSM_TSR_GRID")) {
-            unsigned a = 0, b = 0, c = 0;
-            if (std::sscanf(v, "%u,%u,%u", &a, &b, &c) == 3 && a && b && c && a <= 4096 && b <= 4096 && c <= 4096) {
-                expand = a;
-                collect = b;
-                dl = c;
-            }
-        }
-    }
 };
 
 __global__ __launch_bounds__(kBlock) void k_vcount(const uint32_t* __restrict__ item, uint64_t E,
@@ -1505,6 +1520,1322 @@ struct Replay {
     }
 };
 
+// The environment switches of a TSR mine, read once when it starts (tsr_mine) and held const
+// by its TsrMiner: a mine sees one consistent set, and the next mine on the same context sees
+// the environment as it is then (tests, A/B runs and tuning flip them between mines).
+// [tuning]: swept on MI355X; [test]: a hook that forces a path the tests pin.
+//   FSM_TSR_BITMAP        0: no sid bitmaps (list path).  Read per DB by tsr_finish, not here [test]
+//   FSM_TSR_PAIR_RECS     pair-batch records below which the batch doubles (halves above 4 x),
+//                         [1, 2^30] (2^20) [test: sharded batch agreement]
+//   FSM_TSR_MAX_KIDS      lowers the kept items the bitmap path takes, <= kMaxKids (0: list path) [test]
+//   FSM_TSR_MAX_POS       lowers the itemset index the packed rows take, <= 65535 (list path after
+//                         the rows were counted) [test]
+//   FSM_TSR_BATCH         rules per launch, [1, kMaxBatch] (else kExpBatchWide when the pair
+//                         phase ends at minsup >= kWideMinsup, kExpBatch below) [tuning]
+//   FSM_TSR_PASS_KIDS     lowers the kids per LDS histogram pass, [1, kPassKids] [test: several passes]
+//   FSM_TSR_PART_MB       partial-row budget per launch in MiB, [1, 4096] (32) [tuning]
+//   FSM_TSR_DOMAIN        bitmap | list: every slot's domain by the whole-bitmap AND / by its rarest
+//                         item's list (else by that list's length) [test, A/B]
+//   FSM_TSR_SHARD         0: sharded mines replicate the expansions [test, A/B]
+//   FSM_TSR_SHARD_MIN     expected domain sids from which a launch is sharded (2^18) [tuning]
+//   FSM_TSR_PLIST         0: no kept-row lists [test, A/B]
+//   FSM_TSR_ARENA_MB      the kept-row arena in MiB, fractions taken (else from the free HBM) [test]
+//   FSM_TSR_PLIST_WINDOW  sixteenths of the ring within which a parent's list is read, [1, 16]
+//                         (8; 16 makes the in-flight guard fire) [test]
+//   FSM_TSR_DLMEMO        0: no |sids(X u {c})| memo [test, A/B]
+//   FSM_TSR_DLMEMO_LOG2   log2 of the memo's entries, [4, 28] (24) [test: a table that fills]
+//   FSM_TSR_SETS          launch sets in flight, [2, 4] (kExpSets) [tuning]
+//   FSM_TSR_SPB           bitmap path: expected domain sids per expansion block, [1, 2^20] (kExpSpb) [tuning]
+//   FSM_TSR_PLSPB         parent-list rows per expansion block, [1, 2^20] (kExpSpb) [tuning]
+//   FSM_TSR_TIME_EVERY    every n-th launch records the kernel events, [1, 2^20] (16; 1: bench roofline) [tuning]
+//   FSM_TSR_SPEC          "depth,max": speculation levels [0, 64] and rules per level [1, 4096] (kSpecDepth,
+//                         kSpecMax x the batch; else ignored); a leading 0 turns speculation off [tuning]
+//   FSM_TSR_SPEC_FRAC     speculate the children with support >= frac x the lowest pending rule's,
+//                         (0, 1] (1; else ignored) [tuning]
+//   FSM_TSR_GRID          "expand,collect,dl": the per-launch grids, each [1, 4096] (kExpandBlocks,
+//                         kCollectBlocks, kDlBlocks; else ignored) [tuning]
+struct TsrKnobs {
+    uint64_t pair_recs, part_mb, shard_min, exp_spb, pl_spb;
+    uint32_t max_kids, max_pos, pass_kids;
+    uint32_t batch;  // 0: by the pair phase's final minsup
+    int dom_mode;    // 0 auto (by the rarest item's list length), 1 every slot bitmap, 2 every slot list
+    bool shard, plist, dlmemo, spec_on;
+    bool arena_set;  // arena_mb given
+    double arena_mb, spec_frac = 1.0;
+    int plist_window, dlmemo_log2, nsets;
+    int64_t time_every;
+    int spec_depth = kSpecDepth, spec_max = 0;  // spec_max 0: kSpecMax x the batch
+    TsrGrid grid;
+
+    static TsrKnobs from_env() {
+        auto str = [](const char* name) { const char* v = std::getenv(name); return v ? v : ""; };
+        auto off = [&](const char* name) { return str(name)[0] == '0'; };
+        auto u64 = [](const char* name, uint64_t lo, uint64_t hi, uint64_t dflt) {
+            const char* v = std::getenv(name);
+            return v ? std::clamp<uint64_t>(std::strtoull(v, nullptr, 10), lo, hi) : dflt;
+        };
+        auto i64 = [](const char* name, int64_t lo, int64_t hi, int64_t dflt) {
+            const char* v = std::getenv(name);
+            return v ? std::clamp<int64_t>(std::strtoll(v, nullptr, 10), lo, hi) : dflt;
+        };
+        auto lowered = [](const char* name, uint32_t cap) {
+            const char* v = std::getenv(name);
+            return v ? std::min<uint32_t>(uint32_t(std::strtoul(v, nullptr, 10)), cap) : cap;
+        };
+        TsrKnobs k;
+        k.pair_recs = u64("FSM_TSR_PAIR_RECS", 1, uint64_t(1) << 30, uint64_t(1) << 20);
+        k.max_kids = lowered("FSM_TSR_MAX_KIDS", kMaxKids);
+        k.max_pos = lowered("FSM_TSR_MAX_POS", 0xFFFFu);
+        k.batch = uint32_t(i64("FSM_TSR_BATCH", 1, kMaxBatch, 0));
+        k.pass_kids = uint32_t(u64("FSM_TSR_PASS_KIDS", 1, kPassKids, kPassKids));
+        k.part_mb = u64("FSM_TSR_PART_MB", 1, 4096, 32);
+        k.dom_mode = !std::strcmp(str("FSM_TSR_DOMAIN"), "bitmap") ? 1 : !std::strcmp(str("FSM_TSR_DOMAIN"), "list") ? 2 : 0;
+        k.shard = !off("FSM_TSR_SHARD");
+        k.shard_min = u64("FSM_TSR_SHARD_MIN", 0, ~uint64_t(0), uint64_t(1) << 18);
+        k.plist = !off("FSM_TSR_PLIST");
+        k.arena_set = std::getenv("FSM_TSR_ARENA_MB") != nullptr;
+        k.arena_mb = std::strtod(str("FSM_TSR_ARENA_MB"), nullptr);
+        k.plist_window = int(i64("FSM_TSR_PLIST_WINDOW", 1, 16, 8));
+        k.dlmemo = !off("FSM_TSR_DLMEMO");
+        k.dlmemo_log2 = int(i64("FSM_TSR_DLMEMO_LOG2", 4, 28, 24));
+        k.nsets = int(i64("FSM_TSR_SETS", 2, 4, kExpSets));
+        k.exp_spb = u64("FSM_TSR_SPB", 1, 1u << 20, kExpSpb);
+        k.pl_spb = u64("FSM_TSR_PLSPB", 1, 1u << 20, kExpSpb);
+        k.time_every = i64("FSM_TSR_TIME_EVERY", 1, 1 << 20, 16);
+        k.spec_on = !off("FSM_TSR_SPEC");
+        int sd = 0, sm = 0;
+        if (std::sscanf(str("FSM_TSR_SPEC"), "%d,%d", &sd, &sm) == 2 && sd >= 0 && sd <= 64 && sm > 0 && sm <= 4096) {
+            k.spec_depth = sd;
+            k.spec_max = sm;
+        }
+        const double f = std::atof(str("FSM_TSR_SPEC_FRAC"));
+        if (f > 0.0 && f <= 1.0) k.spec_frac = f;
+        unsigned a = 0, b = 0, c = 0;
+        if (std::sscanf(str("FSM_TSR_GRID"), "%u,%u,%u", &a, &b, &c) == 3 && a && b && c && a <= 4096 && b <= 4096 && c <= 4096)
+            k.grid = TsrGrid{a, b, c};
+        return k;
+    }
+};
+
+// One set of launch buffers: the GPU runs one set's launch while the host commits the results
+// of another.  A set holds the rule descriptors (pinned stage + device copy, one copy per
+// launch), the per-slot control blocks, the histograms (list path: per-slot HBM arrays; bitmap
+// path: per-block partial rows and the domain lists), the results (mapped pinned host memory,
+// at most ecap records per slot) and its own stream and events (completion, per-kernel timing).
+struct ExpSet {
+    DevBuf TL, DL, TR, seen, list, ctl, d_stage, d_dlw, d_ndlw, part, dom;
+    std::unique_ptr<PinnedBuf> stage, pin;
+    Side* h_sides = nullptr;
+    uint64_t *h_drv = nullptr, *h_wave = nullptr;
+    Side* d_sides = nullptr;
+    uint64_t *d_drv = nullptr, *d_wave = nullptr;
+    ExpHdr *h_hdr = nullptr, *d_hdr = nullptr;
+    ExpRec *h_rec = nullptr, *d_rec = nullptr;
+    uint32_t *h_rcnt = nullptr, *d_rcnt = nullptr;  // bitmap path: records per reduce block
+    std::vector<Rule*> batch;
+    std::vector<char> drv_in_x;
+    std::vector<uint64_t> kmono;  // bitmap path: each slot's kept-row list (ring position; kNoList: none)
+    uint64_t amin = kNoList;      // the oldest ring position the launch reads or writes (kNoList: none)
+    bool sharded = false;         // this launch's slots split over the ranks (results gathered)
+    uint32_t la = 0, lz = 0;  // slot sharding: this rank's slots [la, lz) of the batch (else all)
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // 0-4 timing, 5 done
+    // the set's own stream: the sets' launches are independent, so the GPU runs
+    // one set's kernels while the other's are in flight
+    hipStream_t st = nullptr;
+    bool own_stream = false;
+    DevBuf alive;          // kid codes for alive_t (each set its own: k_alive never races a launch)
+    uint32_t alive_t = 0;  // minsup the set's kid codes were built for
+    bool timed = false, busy = false;
+    int depth = 0;        // speculation depth of the batch (0: heap batch)
+    int64_t seq = 0;      // launch number (the older busy set finishes first)
+    uint64_t blocks = 0;  // expansion blocks of the launch
+
+    // the buffers of a mine with B slots per launch (SU = B x U counters per list-path
+    // histogram, part_bytes of partial rows and nrc reduce-block counts on the bitmap path);
+    // the memsets go to the context stream s
+    void alloc(bool use_bm, uint32_t B, uint32_t K, uint32_t ecap, uint64_t SU, uint64_t part_bytes, size_t nrc,
+               hipStream_t s) {
+        const size_t kSidesB = B * sizeof(Side), kOffB = (B + 1) * 8;
+        FSM_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        own_stream = true;
+        if (use_bm) alive.alloc(size_t((K + 15) / 16) * 4);
+        ctl.alloc(B * sizeof(ExpCtl));
+        FSM_HIP(hipMemsetAsync(ctl.p, 0, B * sizeof(ExpCtl), s));
+        if (use_bm) {
+            part.alloc(part_bytes);
+            d_dlw.alloc(uint64_t(B) * ecap * sizeof(uint4));
+        } else {
+            for (DevBuf* b : {&TL, &DL, &TR, &seen, &list}) b->alloc(SU * 4);
+            for (DevBuf* b : {&TL, &DL, &TR, &seen}) FSM_HIP(hipMemsetAsync(b->p, 0, SU * 4, s));
+        }
+        stage = std::make_unique<PinnedBuf>(kSidesB + 2 * kOffB);
+        d_stage.alloc(kSidesB + 2 * kOffB);
+        // [drv offsets | wave offsets | sides]: a launch copies the offsets and its nb sides
+        h_drv = static_cast<uint64_t*>(stage->host);
+        h_wave = h_drv + (B + 1);
+        h_sides = reinterpret_cast<Side*>(static_cast<char*>(stage->host) + 2 * kOffB);
+        d_drv = d_stage.as<uint64_t>();
+        d_wave = d_drv + (B + 1);
+        d_sides = reinterpret_cast<Side*>(d_stage.as<char>() + 2 * kOffB);
+        d_ndlw.alloc(16);
+        // [headers | records, ecap per slot | bitmap path: reduce region counts, B x P x collect]
+        pin = std::make_unique<PinnedBuf>(B * sizeof(ExpHdr) + B * size_t(ecap) * sizeof(ExpRec) + nrc * 4);
+        h_hdr = static_cast<ExpHdr*>(pin->host);
+        h_rec = reinterpret_cast<ExpRec*>(h_hdr + B);
+        h_rcnt = reinterpret_cast<uint32_t*>(h_rec + size_t(B) * ecap);
+        d_hdr = static_cast<ExpHdr*>(pin->dev);
+        d_rec = reinterpret_cast<ExpRec*>(d_hdr + B);
+        d_rcnt = reinterpret_cast<uint32_t*>(d_rec + size_t(B) * ecap);
+        for (int q = 0; q < 5; ++q) FSM_HIP(hipEventCreate(&ev[q]));
+        FSM_HIP(hipEventCreateWithFlags(&ev[5], hipEventDisableTiming));
+    }
+    ~ExpSet() {  // (unwinding: the launch may still be running on buffers about to be freed)
+        if (busy && ev[5]) (void)hipEventSynchronize(ev[5]);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+        if (own_stream && st) {
+            (void)hipStreamSynchronize(st);
+            (void)hipStreamDestroy(st);
+        }
+    }
+};
+
+// Expansion results of rules not yet committed: slots of a pool (Rule::res; a deque,
+// so slots never move; released slots keep their vectors' capacity for the next
+// rule).  Rules in flight carry their launch set in Rule::inset.
+struct ExpResult {
+    std::vector<ExpRec> recs;
+    std::vector<Rule*> preL, preR;  // children created (and expanded) ahead of the commit, by record
+    Rule* owner = nullptr;
+};
+struct ResultPool {
+    std::deque<ExpResult> slots;
+    std::vector<int32_t> free_ids;
+    size_t live = 0, sweep_at = size_t(1) << 16;
+    ExpResult& of(const Rule* r) { return slots[size_t(r->res)]; }  // r->res >= 0
+    ExpResult& get(Rule* r) {
+        if (r->res < 0) {
+            if (free_ids.empty()) {
+                free_ids.push_back(int32_t(slots.size()));
+                slots.emplace_back();
+            }
+            r->res = free_ids.back();
+            free_ids.pop_back();
+            slots[size_t(r->res)].owner = r;
+            ++live;
+        }
+        return slots[size_t(r->res)];
+    }
+    void release(Rule* r) {
+        ExpResult& e = slots[size_t(r->res)];
+        e.recs.clear();
+        e.preL.clear();
+        e.preR.clear();
+        e.owner = nullptr;
+        free_ids.push_back(r->res);
+        r->res = -1;
+        --live;
+    }
+    void sweep(uint32_t minsup) {  // results of rules now below minsup can never be committed
+        if (live <= sweep_at) return;
+        for (ExpResult& e : slots)
+            if (e.owner && e.owner->sup < minsup) release(e.owner);
+        sweep_at = std::max<size_t>(2 * live, 1u << 16);
+    }
+};
+
+// Speculated rules wait in `pending` (ordered like the heap, results
+// cached or in flight) instead of going back to the heap: the next rule to
+// commit is always the larger of the heap top and the pending front, which
+// is exactly the one-at-a-time order; new rules only ever enter the heap.
+// The rules of one batch pop leave the heap in its order, so `pending` is a
+// merge of sorted runs (one per pop loop): a small heap of runs keyed by their
+// fronts, no per-rule tree node.
+struct PendingRuns {
+    const RuleStore* st;
+    struct Run {
+        std::vector<Rule*> v;  // largest first
+        size_t h = 0;          // front
+    };
+    std::vector<Run> runs;
+    std::vector<int> free_ids, heap;  // heap: live runs, the largest front on top
+    bool front_less(int a, int b) const {
+        return rule_cmp(*st, runs[size_t(a)].v[runs[size_t(a)].h], runs[size_t(b)].v[runs[size_t(b)].h]) < 0;
+    }
+    bool empty() const { return heap.empty(); }
+    Rule* front() const { return runs[size_t(heap[0])].v[runs[size_t(heap[0])].h]; }
+    void pop() {
+        auto cmp = [this](int a, int b) { return front_less(a, b); };
+        const int id = heap[0];
+        std::pop_heap(heap.begin(), heap.end(), cmp);
+        heap.pop_back();
+        Run& r = runs[size_t(id)];
+        if (++r.h < r.v.size()) {
+            heap.push_back(id);
+            std::push_heap(heap.begin(), heap.end(), cmp);
+        } else {
+            r.v.clear();
+            r.h = 0;
+            free_ids.push_back(id);
+        }
+    }
+    void add(std::vector<Rule*>& v) {  // v: in heap pop order; taken over (left empty)
+        if (v.empty()) return;
+        int id;
+        if (free_ids.empty()) {
+            id = int(runs.size());
+            runs.emplace_back();
+        } else {
+            id = free_ids.back();
+            free_ids.pop_back();
+        }
+        runs[size_t(id)].v.swap(v);
+        runs[size_t(id)].h = 0;
+        v.clear();
+        heap.push_back(id);
+        std::push_heap(heap.begin(), heap.end(), [this](int a, int b) { return front_less(a, b); });
+    }
+    uint32_t min_sup() const {  // support of the smallest pending rule (the runs' backs)
+        uint32_t m = 0xFFFFFFFFu;
+        for (int id : heap) m = std::min(m, runs[size_t(id)].v.back()->sup);
+        return m;
+    }
+};
+
+// What a mine counts: the fsm_stats fields, the kstats rows and the verbose lines
+struct TsrCounters {
+    struct Seg {
+        double ms = 0;  // over the timed launches
+        int64_t n = 0, timed = 0, bytes = 0, survey = 0;  // survey: SURVEY §8(d) TSR units
+    } seg[4];  // bitmap path: domain, rows, reduce, k_dl; list path: expansion, -, collect, k_publish
+    uint64_t pair_exchanged = 0;  // union keys exchanged (verbose)
+    int64_t expansions = 0, launches = 0, spec_pushback = 0, gpu_rules = 0;
+    // child speculation: rules made, their launches, committed, and dropped at their parent's commit (verbose)
+    int64_t spec_made = 0, spec_launches = 0, spec_hit = 0, spec_waste = 0;
+    int64_t exp_domain = 0, exp_entries = 0, exp_bitmap_bytes = 0, exp_part_bytes = 0;
+    int64_t exp_hold = 0, exp_walk = 0;  // domain rows where the rule holds, row entries walked (verbose)
+    int64_t exp_plist = 0;               // expansions whose domain came from the parent's kept rows (verbose)
+    int64_t ring_waits = 0;              // launches in flight finished early to free their ring positions
+    double wait_ms = 0;  // host time blocked on the GPU in the expansion loop
+    double prep_ms = 0, post_ms = 0, commit_ms = 0, pop_ms = 0;  // host time split (verbose summary)
+    double fill_ms = 0;  // launch prep: descriptor fill (the rest is the HIP calls)
+    double last_log_ms = 0;  // verbose progress line every 20 s
+};
+
+// One TSR mine: its knobs, the replay, the device buffers and the launch sets.  tsr_mine
+// lists the stages.
+struct TsrMiner {
+    const TsrKnobs kn;
+    fsm_ctx* const ctx;
+    fsm_db* const db;
+    TsrDevDB* const d;
+    const hipStream_t s;  // the context stream (the launches run on the sets' own)
+    const double minconf, t0;
+    const uint32_t U;
+    const uint64_t N;
+    const std::vector<uint32_t>& sup;  // |sids(item)|
+    Replay rp;
+    std::vector<uint64_t> voff;
+    // nranks > 1: each rank counts the pairs of its own sequence range [slo, shi); the candidate
+    // keys are exchanged and their partial counts summed.  A failure on one
+    // rank is agreed on before each collective, so no peer is left blocked.
+    Comm* const comm;
+    const bool shard;
+    const int R;
+    const uint32_t slo, shi;
+    Agreement agr;
+    std::vector<PairRec> recs;  // pair phase: the batch's records
+    uint64_t scr_items = 0;     // pair phase: item rows of scr
+    // The expansions see only the items that can still be in a rule: support >=
+    // the pair phase's minsup, which only rises from here (K "kept" items).
+    std::vector<uint32_t> kept_items, h_kid_of;  // h_kid_of: bitmap path, item -> kid
+    uint32_t K = 0;
+    bool use_bm = false;
+    uint64_t E2 = 0;  // kept row entries
+    double t1 = 0;    // the pair phase and the kept rows done
+    // launch geometry (size_launches): B rules per launch, at most ecap records per slot (one per
+    // candidate item); bitmap path: P LDS histogram passes of KP kids, dense partial rows of
+    // 2 * KP counters (row_bytes) per expansion block, at most max_blocks blocks per launch
+    uint32_t B = 0, ecap = 0, KP = 0, P = 0;
+    uint64_t row_bytes = 0, max_blocks = 0;
+    size_t xlds = 0;
+    int spec_max = 0;
+    bool shard_exp = false, plist = false;
+    uint64_t acap = 0;          // arena entries (16 B)
+    uint64_t ahead = 0;         // the ring's head (entries written, monotonic; a list's position mod acap)
+    uint64_t plist_window = 0;  // a child reads its parent's list while it lies within this many entries of the head
+    DlMemo memo{nullptr, 0u};
+    const char* seg_name[4] = {"", "", "", ""};
+    ResultPool results;
+    PendingRuns pending;
+    std::vector<std::pair<std::vector<Rule*>, int>> spec_todo;  // finished launches whose children to speculate
+    int64_t seq_next = 0;
+    TsrCounters c;
+    DevBuf d_sup, scr, arena, memo_buf;
+    DevBuf k_off, k_item, k_first, k_last, k_sup;  // list path rows (SoA)
+    DevBuf k_ent, d_kidof, d_kept, d_ksup;  // bitmap path rows (packed) and kid tables
+    DevBuf d_rdir, d_kvoff, d_vfl;          // bitmap path: rank directories and vertical entries of the kids
+    // The launch sets stay the LAST member: ~ExpSet waits for a launch in flight, whose kernels
+    // use the arena, the memo, the k_* rows, the kid tables and d_sup above, so the sets must be
+    // destroyed before all of them (members die in reverse order of declaration).
+    std::unique_ptr<ExpSet[]> xs;
+
+    TsrMiner(const TsrKnobs& knobs, fsm_ctx* ctx_, fsm_db* db_, int32_t k, double mc, double t0_)
+        : kn(knobs), ctx(ctx_), db(db_), d(db_->tsr_dev), s(ctx_->stream), minconf(mc), t0(t0_), U(uint32_t(d->U)),
+          N(uint64_t(d->N)), sup(d->sup), rp{k, mc}, voff(size_t(U) + 1), comm(ctx_->comm),
+          shard(comm && comm->nranks() > 1), R(shard ? comm->nranks() : 1),
+          slo(shard ? uint32_t(uint64_t(d->N) * uint64_t(comm->rank()) / uint64_t(R)) : 0u),
+          shi(shard ? uint32_t(uint64_t(d->N) * uint64_t(comm->rank() + 1) / uint64_t(R)) : uint32_t(d->N)),
+          pending{&rp.st, {}, {}, {}} {
+        rp.xin.init(U);
+        agr.comm = shard ? comm : nullptr;
+        agr.what = "TSR";
+        FSM_HIP(hipMemcpyAsync(voff.data(), d->vert_off.p, (size_t(U) + 1) * 8, hipMemcpyDeviceToHost, s));
+        d_sup.alloc(size_t(std::max<uint32_t>(U, 1)) * 4);
+        FSM_HIP(hipMemcpyAsync(d_sup.p, d->sup.data(), size_t(U) * 4, hipMemcpyHostToDevice, s));
+        FSM_HIP(hipStreamSynchronize(s));
+    }
+
+    // ---------------- pair phase (i ascending, j > i; IJ then JI)
+    struct PairBatch {
+        uint32_t a, nb;  // items [a, a + nb)
+        uint32_t t;      // minsup when the batch started
+        uint32_t tq;     // compaction threshold: t, or ceil(t / R) for a rank's partial counts (a pair
+                         // whose total reaches t has a partial >= t / R on some rank)
+        std::vector<uint64_t> hoff;  // item a + g's records: recs[hoff[g], hoff[g + 1])
+        std::vector<PairRec> mine;   // sharded: this rank's candidates
+        uint64_t nrec = 0;
+    };
+    void pair_phase() {
+        uint32_t nb_items = 16;
+        // the batch grows while a batch's candidate records stay below pair_recs and
+        // shrinks above 4 x pair_recs
+        const uint64_t scr_cap_items =
+            std::max<uint64_t>(1, (uint64_t(256) << 20) / (uint64_t(std::max<uint32_t>(U, 1)) * 8));
+        for (uint32_t a = 0; a < U;) {
+            PairBatch pb;
+            pb.a = a;
+            pb.nb = uint32_t(std::min<uint64_t>({uint64_t(nb_items), uint64_t(U - a), scr_cap_items}));
+            pb.t = rp.minsup;
+            pb.tq = shard ? (pb.t + uint32_t(R) - 1) / uint32_t(R) : pb.t;
+            pb.hoff.assign(size_t(pb.nb) + 1, 0);
+            // this rank's counts of the batch (rank-local work: deferred on failure when sharded)
+            agr.run([&] { count_pairs(pb); });
+            // nadapt drives the next batch size (must be alike on every rank)
+            const uint64_t nadapt = shard ? exchange_pairs(pb) : pb.nrec;
+            register_pairs(pb);
+            if (nadapt < kn.pair_recs) nb_items = std::min<uint32_t>(nb_items * 2, 4096);
+            else if (nadapt > 4 * kn.pair_recs && nb_items > 1) nb_items /= 2;
+            a += pb.nb;
+        }
+        scr.release();
+    }
+    void count_pairs(PairBatch& pb) {
+        const uint32_t a = pb.a, nb = pb.nb, b = a + nb;
+        const unsigned grid = unsigned((uint64_t(nb) * 64 + kBlock - 1) / kBlock);
+        if (shard) agr.maybe_inject("pairs");
+        if (scr_items < nb) {
+            scr.alloc(uint64_t(nb) * U * 8);
+            FSM_HIP(hipMemsetAsync(scr.p, 0, uint64_t(nb) * U * 8, s));
+            scr_items = nb;
+        }
+        const uint64_t v0 = voff[a], v1 = voff[b];
+        if (v1 > v0) {
+            hipLaunchKernelGGL(k_pairs, dim3(unsigned((v1 - v0 + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
+                               d->vert_sid.as<uint32_t>(), d->vert_item.as<uint32_t>(), v0, v1, a, U, pb.t, slo, shi,
+                               d_sup.as<uint32_t>(), d->row_off.as<uint32_t>(), d->item.as<uint32_t>(),
+                               d->first.as<uint32_t>(), d->last.as<uint32_t>(), scr.as<uint32_t>());
+            FSM_LAUNCHED("k_pairs", s);
+        }
+        DevBuf rowcnt(size_t(nb) * 4 + 4), rowoff((size_t(nb) + 1) * 8);
+        hipLaunchKernelGGL(k_pairs_compact, dim3(grid), dim3(kBlock), 0, s, scr.as<uint32_t>(), a, nb, U, pb.tq,
+                           rowcnt.as<uint32_t>(), rowoff.as<uint64_t>(), (PairRec*)nullptr, 0);
+        FSM_LAUNCHED("k_pairs_compact", s);
+        scan_exclusive(rowcnt.as<uint32_t>(), rowoff.as<uint64_t>(), nb, s);
+        FSM_HIP(hipMemcpyAsync(pb.hoff.data(), rowoff.p, (size_t(nb) + 1) * 8, hipMemcpyDeviceToHost, s));
+        FSM_HIP(hipStreamSynchronize(s));
+        pb.nrec = pb.hoff[nb];
+        DevBuf d_recs(std::max<uint64_t>(pb.nrec, 1) * sizeof(PairRec));
+        // unsharded: the compaction also re-zeroes the counters it visits; sharded: the
+        // counters are read again for the union's partials
+        hipLaunchKernelGGL(k_pairs_compact, dim3(grid), dim3(kBlock), 0, s, scr.as<uint32_t>(), a, nb, U, pb.tq,
+                           rowcnt.as<uint32_t>(), rowoff.as<uint64_t>(), d_recs.as<PairRec>(), shard ? 0 : 1);
+        FSM_LAUNCHED("k_pairs_compact", s);
+        std::vector<PairRec>& dst = shard ? pb.mine : recs;
+        dst.resize(pb.nrec);
+        if (pb.nrec)
+            FSM_HIP(hipMemcpyAsync(dst.data(), d_recs.p, pb.nrec * sizeof(PairRec), hipMemcpyDeviceToHost, s));
+        FSM_HIP(hipStreamSynchronize(s));
+    }
+    // sharded: candidate keys of this rank -> union over ranks -> every rank's partials of
+    // the union summed -> the exact counts, kept at t like the one-rank compaction.  Returns
+    // the union's size: the same number on every rank
+    uint64_t exchange_pairs(PairBatch& pb) {
+        const uint32_t a = pb.a, nb = pb.nb, b = a + nb, t = pb.t;
+        agr.agree(s);
+        std::vector<uint8_t> blob(pb.mine.size() * 8);
+        for (size_t q = 0; q < pb.mine.size(); ++q) {
+            std::memcpy(blob.data() + q * 8, &pb.mine[q].i, 4);
+            std::memcpy(blob.data() + q * 8 + 4, &pb.mine[q].j, 4);
+        }
+        std::vector<size_t> sizes;
+        const std::vector<uint8_t> all = comm->gather_blobs(blob, sizes, s);
+        std::vector<uint2> keys(all.size() / 8);
+        for (size_t q = 0; q < keys.size(); ++q) std::memcpy(&keys[q], all.data() + q * 8, 8);
+        std::sort(keys.begin(), keys.end(),
+                  [](const uint2& x, const uint2& y) { return x.x != y.x ? x.x < y.x : x.y < y.y; });
+        keys.erase(std::unique(keys.begin(), keys.end(),
+                               [](const uint2& x, const uint2& y) { return x.x == y.x && x.y == y.y; }),
+                   keys.end());
+        std::vector<uint32_t> part(keys.size() * 2, 0u);
+        agr.run([&] {
+            for (const uint2& kk : keys)  // every rank batched [a, b) alike
+                if (kk.x < a || kk.x >= b || kk.y >= U)
+                    throw Error(FSM_EDEVICE, "TSR sharded pair phase: exchanged key outside the batch");
+            if (!keys.empty()) {
+                DevBuf d_keys(keys.size() * 8), d_part(keys.size() * 8);
+                FSM_HIP(hipMemcpyAsync(d_keys.p, keys.data(), keys.size() * 8, hipMemcpyHostToDevice, s));
+                hipLaunchKernelGGL(k_pairs_gather, dim3(unsigned((keys.size() + kBlock - 1) / kBlock)),
+                                   dim3(kBlock), 0, s, scr.as<uint32_t>(), a, U, d_keys.as<uint2>(),
+                                   uint32_t(keys.size()), d_part.as<uint32_t>());
+                FSM_LAUNCHED("k_pairs_gather", s);
+                FSM_HIP(hipMemcpyAsync(part.data(), d_part.p, keys.size() * 8, hipMemcpyDeviceToHost, s));
+            }
+            FSM_HIP(hipMemsetAsync(scr.p, 0, uint64_t(nb) * U * 8, s));
+            FSM_HIP(hipStreamSynchronize(s));
+        });
+        agr.agree(s);
+        comm->host_allreduce_u32(part.data(), part.size(), s);
+        recs.clear();
+        std::fill(pb.hoff.begin(), pb.hoff.end(), 0);
+        for (size_t q = 0; q < keys.size(); ++q) {
+            const uint32_t ij = part[2 * q], ji = part[2 * q + 1];
+            if (ij < t && ji < t) continue;
+            recs.push_back(PairRec{keys[q].x, keys[q].y, ij, ji});
+            pb.hoff[keys[q].x - a + 1] += 1;
+        }
+        for (uint32_t g = 0; g < nb; ++g) pb.hoff[g + 1] += pb.hoff[g];
+        c.pair_exchanged += keys.size();
+        return keys.size();
+    }
+    // the batch's rules saved and registered, in (i, j) order against the rising minsup
+    void register_pairs(const PairBatch& pb) {
+        for (uint32_t g = 0; g < pb.nb; ++g) {
+            const uint32_t i = pb.a + g;
+            if (sup[i] < rp.minsup) continue;
+            for (uint64_t q = pb.hoff[g]; q < pb.hoff[g + 1]; ++q) {
+                const PairRec& pr = recs[q];
+                const uint32_t j = pr.j;
+                if (sup[j] < rp.minsup) continue;
+                if (pr.ij >= rp.minsup) take(rp.derive(nullptr, i, j, pr.ij, sup[i]), true);
+                if (pr.ji >= rp.minsup) take(rp.derive(nullptr, j, i, pr.ji, sup[j]), true);
+            }
+        }
+    }
+    // a valid rule: among the top k when confident enough, and a candidate for expansion
+    void take(Rule* r, bool lr) {
+        if (r->conf >= minconf) rp.save(r);
+        rp.reg(r, lr);
+    }
+
+    // ---------------- kept rows
+    // Rows cut to the kept items: the count pass (rc), the scan of the row lengths, E2 read
+    // back, k_off32, the fill pass (off64).  ready() follows the E2 read-back: it waits for
+    // the stream and allocates the rows, or returns false (nothing is written then).
+    template <class Count, class Ready, class Fill> bool build_rows(Count&& count, Ready&& ready, Fill&& fill) {
+        DevBuf rc(std::max<uint64_t>(N, 1) * 4), off64((N + 1) * 8);
+        if (N) count(rc.as<uint32_t>());
+        scan_exclusive(rc.as<uint32_t>(), off64.as<uint64_t>(), N, s);
+        FSM_HIP(hipMemcpyAsync(&E2, off64.as<uint64_t>() + N, 8, hipMemcpyDeviceToHost, s));
+        if (!ready()) return false;
+        hipLaunchKernelGGL(k_off32, dim3(unsigned(std::min<uint64_t>((N + 256) / 256, 4096))), dim3(256), 0, s,
+                           off64.as<uint64_t>(), N, k_off.as<uint32_t>());
+        FSM_LAUNCHED("k_off32", s);
+        if (N) fill(off64.as<uint64_t>());
+        return true;
+    }
+    void keep_rows() {
+        for (uint32_t it = 0; it < U; ++it)
+            if (sup[it] >= rp.minsup) kept_items.push_back(it);
+        K = uint32_t(kept_items.size());
+        // bitmap path: sid bitmaps built, K <= kMaxKids, itemset indexes < 2^16 (packed rows)
+        use_bm = d->bm.p != nullptr && K > 0 && K <= kn.max_kids;
+        const unsigned rows_grid = unsigned(std::min<uint64_t>((N * 64 + kBlock - 1) / kBlock, 65536));
+        if (use_bm) use_bm = pack_rows(rows_grid);
+        if (!use_bm) keep_rows_list(rows_grid);
+        t1 = now_ms();
+        if (ctx->opts.verbose)
+            std::fprintf(stderr, "[fsm tsr] pair phase %.0f ms: minsup %u, candidates %zu, rules %zu, kept items %u, "
+                         "row entries %llu, %s path (ranks %d, keys exchanged %llu)\n",
+                         t1 - t0, rp.minsup, rp.cand.size(), rp.krules.size(), K, (unsigned long long)E2,
+                         use_bm ? "bitmap" : "list", R, (unsigned long long)c.pair_exchanged);
+    }
+    // bitmap path: the kid tables, the packed rows, and the kept items' rank directories and
+    // vertical entries; false (the list path takes the mine) when an itemset index or the
+    // entry count does not fit the packed form
+    bool pack_rows(unsigned rows_grid) {
+        h_kid_of.assign(U, kNone);
+        std::vector<uint32_t> ksup(K);
+        for (uint32_t q = 0; q < K; ++q) {
+            h_kid_of[kept_items[q]] = q;
+            ksup[q] = sup[kept_items[q]];
+        }
+        d_kidof.alloc(size_t(std::max<uint32_t>(U, 1)) * 4);
+        d_kept.alloc(size_t(K) * 4);
+        d_ksup.alloc(size_t(K) * 4);
+        FSM_HIP(hipMemcpyAsync(d_kidof.p, h_kid_of.data(), size_t(U) * 4, hipMemcpyHostToDevice, s));
+        FSM_HIP(hipMemcpyAsync(d_kept.p, kept_items.data(), size_t(K) * 4, hipMemcpyHostToDevice, s));
+        FSM_HIP(hipMemcpyAsync(d_ksup.p, ksup.data(), size_t(K) * 4, hipMemcpyHostToDevice, s));
+        DevBuf mpos(4);
+        FSM_HIP(hipMemsetAsync(mpos.p, 0, 4, s));
+        auto pack = [&](uint32_t* rc, uint32_t* mp, const uint64_t* off, uint2* ent) {
+            hipLaunchKernelGGL(k_rows_pack, dim3(rows_grid), dim3(kBlock), 0, s, d->row_off.as<uint32_t>(),
+                               d->item.as<uint32_t>(), d->first.as<uint32_t>(), d->last.as<uint32_t>(),
+                               d_kidof.as<uint32_t>(), N, rc, mp, off, ent);
+            FSM_LAUNCHED("k_rows_pack", s);
+        };
+        const bool packed = build_rows(
+            [&](uint32_t* rc) { pack(rc, mpos.as<uint32_t>(), (const uint64_t*)nullptr, (uint2*)nullptr); },
+            [&] {
+                uint32_t maxpos = 0;
+                FSM_HIP(hipMemcpyAsync(&maxpos, mpos.p, 4, hipMemcpyDeviceToHost, s));
+                FSM_HIP(hipStreamSynchronize(s));
+                if (maxpos > kn.max_pos || E2 >= kNone) return false;  // an itemset index past 2^16
+                k_off.alloc((N + 1) * 4);
+                k_ent.alloc(std::max<uint64_t>(E2, 1) * 8);
+                return true;
+            },
+            [&](const uint64_t* off64) { pack((uint32_t*)nullptr, (uint32_t*)nullptr, off64, k_ent.as<uint2>()); });
+        if (!packed) return false;
+        // the kept items' rank directories and vertical entries (k_exp_domain's probes)
+        std::vector<uint32_t> kvoff(size_t(K) + 1, 0);
+        for (uint32_t q = 0; q < K; ++q) kvoff[q + 1] = kvoff[q] + ksup[q];
+        if (kvoff[K] != E2) throw Error(FSM_EDEVICE, "TSR: kept row entries differ from the kept supports");
+        d_kvoff.alloc((size_t(K) + 1) * 4);
+        FSM_HIP(hipMemcpyAsync(d_kvoff.p, kvoff.data(), (size_t(K) + 1) * 4, hipMemcpyHostToDevice, s));
+        d_rdir.alloc(std::max<size_t>(size_t(K) * (d->NW / 4) * 4, 4));
+        hipLaunchKernelGGL(k_rank_dir, dim3(K), dim3(kBlock), 0, s, d->bm.as<uint32_t>(), d->NW,
+                           d_kept.as<uint32_t>(), d_rdir.as<uint32_t>());
+        FSM_LAUNCHED("k_rank_dir", s);
+        d_vfl.alloc(std::max<uint64_t>(E2, 1) * 8);
+        if (N) {
+            hipLaunchKernelGGL(k_vfl, dim3(unsigned(std::min<uint64_t>((N + kBlock - 1) / kBlock, 65536))),
+                               dim3(kBlock), 0, s, k_off.as<uint32_t>(), k_ent.as<uint2>(), uint32_t(N),
+                               d->bm.as<uint32_t>(), d->NW, d_kept.as<uint32_t>(), d_rdir.as<uint32_t>(),
+                               d_kvoff.as<uint32_t>(), d_vfl.as<uint2>());
+            FSM_LAUNCHED("k_vfl", s);
+        }
+        FSM_HIP(hipStreamSynchronize(s));
+        return true;
+    }
+    // list path: rows restricted to the kept items, SoA with each entry's item support
+    void keep_rows_list(unsigned rows_grid) {
+        auto keep = [&](uint32_t* rc, const uint64_t* off, uint32_t* o_item, uint32_t* o_first, uint32_t* o_last,
+                        uint32_t* o_sup) {
+            hipLaunchKernelGGL(k_rows_keep, dim3(rows_grid), dim3(kBlock), 0, s, d->row_off.as<uint32_t>(),
+                               d->item.as<uint32_t>(), d->first.as<uint32_t>(), d->last.as<uint32_t>(),
+                               d_sup.as<uint32_t>(), rp.minsup, N, rc, off, o_item, o_first, o_last, o_sup);
+            FSM_LAUNCHED("k_rows_keep", s);
+        };
+        build_rows(
+            [&](uint32_t* rc) {
+                keep(rc, (const uint64_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
+                     (uint32_t*)nullptr);
+            },
+            [&] {
+                FSM_HIP(hipStreamSynchronize(s));
+                k_off.alloc((N + 1) * 4);
+                for (DevBuf* b : {&k_item, &k_first, &k_last, &k_sup}) b->alloc(std::max<uint64_t>(E2, 1) * 4);
+                return true;
+            },
+            [&](const uint64_t* off64) {
+                keep((uint32_t*)nullptr, off64, k_item.as<uint32_t>(), k_first.as<uint32_t>(), k_last.as<uint32_t>(),
+                     k_sup.as<uint32_t>());
+            });
+        FSM_HIP(hipStreamSynchronize(s));
+    }
+
+    // ---------------- launch sets
+    // Batched speculation, committed in the exact sequential order: the next
+    // B candidates (in heap order) are expanded together on the GPU;
+    // they are committed one by one while each is still the heap maximum; when
+    // a newly registered rule outranks the next one, the rest go back to the
+    // heap with their results cached (results are minsup-independent supersets,
+    // re-filtered against the current minsup at commit), so no expansion is
+    // computed twice and the outcome equals the one-at-a-time replay.
+    void size_launches() {
+        // Rules per launch.  Wide batches halve the launches (round trips) where supports are
+        // coarse: at c4 (pair-phase minsup in the hundreds) every speculated rule is committed,
+        // and 768 rules per launch take 12,973 launches down to 7,179 (2.76 -> 2.39 s).  Where
+        // supports are a few units (the 5K prefix ends at minsup 2) a wide batch's lowest rules
+        // sit at the threshold, their speculated children mostly fall below the rising minsup
+        // (1.45M speculated, 0.22M committed) and the launches multiply (2.6K -> 15K): those
+        // mines keep kExpBatch.
+        B = kn.batch ? kn.batch : uint32_t(rp.minsup >= kWideMinsup ? kExpBatchWide : kExpBatch);
+        spec_max = kn.spec_max ? kn.spec_max : kSpecMax * int(B);
+        ecap = use_bm ? std::max<uint32_t>(K, 1) : std::max<uint32_t>(U, 1);
+        KP = use_bm ? std::min<uint32_t>(K, kn.pass_kids) : 0u;
+        P = use_bm ? (K + KP - 1) / KP : 0u;
+        row_bytes = uint64_t(P) * 2 * KP * 4;
+        const uint64_t part_budget = std::max<uint64_t>(kn.part_mb << 20, uint64_t(B) * row_bytes);
+        max_blocks = use_bm ? part_budget / row_bytes : 0;
+        xlds = use_bm ? (size_t(2) * KP + (K + 15) / 16) * 4 : 0;
+        // Sharded TSR (nranks > 1, bitmap path): a launch whose expected domain (sum of 2 sup + 1
+        // over its rules) reaches kn.shard_min has its slots split over the ranks and their
+        // results all-gathered once (finish); smaller launches run replicated on every rank (no
+        // gather: DESIGN.md §6).  The replay stays replicated and deterministic
+        shard_exp = shard && use_bm && kn.shard;
+        // Kept-row lists (bitmap path): an expansion keeps the rows where its rule holds with a
+        // non-empty suffix (sid, firstX | lastY, max X / max Y positions) in a per-mine device
+        // arena; a child rule's domain is then its parent's list with only the added item probed
+        // (a child holds only where its parent does).  The lists are rank-local; a rule whose
+        // parent list is not at hand probes the bitmaps, and the counts are the same either way.
+        // The arena is a ring: a launch writes its rules' lists (each at most the rule's support)
+        // at the head, at most acap / (4 nsets) entries (else it keeps none).  A launch may stay
+        // in flight while later launches advance the head, so each set records the oldest ring
+        // position it reads or writes (ExpSet::amin), see reserve_ring
+        plist = use_bm && kn.plist;
+        if (plist) {
+            size_t fr = 0, tot = 0;
+            FSM_HIP(hipMemGetInfo(&fr, &tot));
+            // lists for about the whole mine: the rows where a rule holds summed over the expansions
+            // reach a few thousand per sequence (c4: 2.0 G entries)
+            acap = std::min<uint64_t>({fr / (4 * uint64_t(ctx->dev_share)), uint64_t(64) << 30,
+                                       std::max<uint64_t>(uint64_t(64) << 20, uint64_t(d->NW) * 32 * 4096 * sizeof(uint4))}) /
+                   sizeof(uint4);
+            if (kn.arena_set) acap = uint64_t(kn.arena_mb * double(1u << 20)) / sizeof(uint4);
+            if (acap) arena.alloc(acap * sizeof(uint4));
+        }
+        // acap / 2 by default: every list a launch in flight reads stays clear of the later
+        // launches' writes (16/16: read while no later write has reached it, the guard's case)
+        plist_window = acap / 16 * uint64_t(kn.plist_window);
+        // |sids(X u {c})| memo (bitmap path): zeroed once per mine
+        if (use_bm && kn.dlmemo) {
+            const uint32_t ent = 1u << kn.dlmemo_log2;  // (2^24 entries: 256 MiB)
+            memo_buf.alloc(size_t(ent) * sizeof(uint4));
+            FSM_HIP(hipMemsetAsync(memo_buf.p, 0, size_t(ent) * sizeof(uint4), s));
+            FSM_HIP(hipStreamSynchronize(s));  // (the launches run on the sets' own streams)
+            memo = DlMemo{memo_buf.as<uint4>(), ent - 1u};
+        }
+        const char* names[2][4] = {{"k_expand", "", "k_expand_collect", "k_publish"},
+                                   {"k_exp_domain", "k_exp_rows", "k_expand_reduce", "k_dl"}};
+        for (int q = 0; q < 4; ++q) seg_name[q] = names[use_bm ? 1 : 0][q];
+    }
+    void alloc_sets() {
+        xs.reset(new ExpSet[kn.nsets]);
+        const uint64_t SU = uint64_t(B) * std::max<uint32_t>(U, 1);
+        const size_t nrc = use_bm ? size_t(B) * P * kn.grid.collect : 0;
+        for (int xi = 0; xi < kn.nsets; ++xi) xs[xi].alloc(use_bm, B, K, ecap, SU, max_blocks * row_bytes, nrc, s);
+        FSM_HIP(hipStreamSynchronize(s));  // the DB, kid tables and set buffers are ready for the set streams
+        c.last_log_ms = now_ms();
+    }
+
+    // ---------------- launch
+    // expand `batch` on a free set (finishing the oldest busy one first when all are
+    // busy): enqueue the launch and return; finish() takes the results in
+    void launch(const std::vector<Rule*>& batch, int depth) {
+        ExpSet& x = free_set();
+        const double tl0 = now_ms();
+        x.batch = batch;
+        x.depth = depth;
+        x.seq = seq_next++;
+        for (Rule* r : batch) {
+            r->inset = int8_t(&x - xs.get());
+            // every rule of the batch (not only this rank's slots): its children's X ids derive from it
+            if (r->xid == kNone) r->xid = rp.xin.get(r->pxid, rp.st.X(r)[r->nx - 1]);
+        }
+        split_slots(x);
+        const uint32_t nb = x.lz - x.la;  // slots launched here
+        const Rule* const* bp = batch.data() + x.la;
+        c.gpu_rules += nb;
+        fill_sides(x, bp, nb);
+        reserve_ring(x, bp, nb);
+        fit_blocks(x, nb);
+        x.blocks = x.h_wave[nb];
+        if (use_bm && x.dom.bytes < x.h_drv[nb] * 4)
+            x.dom.alloc(std::max<uint64_t>(x.h_drv[nb] * 4 * 5 / 4, uint64_t(1) << 20));
+        c.fill_ms += now_ms() - tl0;
+        enqueue(x, nb);
+        c.prep_ms += now_ms() - tl0;
+    }
+    ExpSet& free_set() {
+        for (int xi = 0; xi < kn.nsets; ++xi)
+            if (!xs[xi].busy) return xs[xi];
+        ExpSet* xp = &xs[0];  // every set busy: the oldest launch finishes first
+        for (int xi = 1; xi < kn.nsets; ++xi)
+            if (xs[xi].seq < xp->seq) xp = &xs[xi];
+        finish(*xp);
+        return *xp;
+    }
+    // slot sharding: this rank expands only its contiguous share [la, lz) of the batch, split so
+    // that the shares' expected domains (about twice each rule's support) are equal
+    void split_slots(ExpSet& x) {
+        const std::vector<Rule*>& batch = x.batch;
+        x.la = 0;
+        x.lz = uint32_t(batch.size());
+        x.sharded = false;
+        uint64_t tot = 0;
+        if (shard_exp)
+            for (Rule* r : batch) tot += 2ull * r->sup + 1;
+        if (shard_exp && tot >= kn.shard_min) {
+            x.sharded = true;
+            const uint64_t lo = tot * uint64_t(comm->rank()) / uint64_t(R), hi = tot * uint64_t(comm->rank() + 1) / uint64_t(R);
+            uint64_t acc = 0;
+            x.la = x.lz = uint32_t(batch.size());
+            for (uint32_t k = 0; k < batch.size(); ++k) {  // slot k belongs to the rank whose range holds its start
+                if (acc >= lo && x.la == batch.size()) x.la = k;
+                if (acc >= hi) { x.lz = k; break; }
+                acc += 2ull * batch[k]->sup + 1;
+            }
+            if (x.lz < x.la) x.lz = x.la;
+        }
+    }
+    // the item of least support among `best` and it[0, n) (`best`, then the earlier, on ties)
+    uint32_t rarest(const uint32_t* it, uint32_t n, uint32_t best) const {
+        for (uint32_t q = 0; q < n; ++q)
+            if (sup[it[q]] < sup[best]) best = it[q];
+        return best;
+    }
+    // descriptors written in place into the set's pinned stage (only the used items:
+    // the kernels read X[0, nx) and Y[0, ny)), with the slots' block (wave) and domain offsets
+    void fill_sides(ExpSet& x, const Rule* const* bp, uint32_t nb) {
+        x.h_drv[0] = x.h_wave[0] = 0;
+        x.drv_in_x.assign(nb, 1);
+        for (uint32_t k = 0; k < nb; ++k) {
+            const Rule* r = bp[k];
+            const uint32_t *rx = rp.st.X(r), *ry = rp.st.Y(r);
+            Side& sd = x.h_sides[k];
+            sd.nx = r->nx;
+            sd.ny = r->ny;
+            sd.doL = r->expandLR;
+            sd.doR = 1;
+            sd.maxX = rx[r->nx - 1];
+            sd.maxY = ry[r->ny - 1];
+            std::copy(rx, rx + r->nx, sd.X);
+            std::copy(ry, ry + r->ny, sd.Y);
+            sd.pc = sd.pleft = sd.pn = sd.kb = 0;
+            sd.pl = 0;
+            sd.ko = kNoList;
+            sd.xid = r->xid;  // (the memo key of its left extensions)
+            sd.klo = use_bm ? std::min(h_kid_of[rx[r->nx - 1]], h_kid_of[ry[r->ny - 1]]) + 1u : 0u;
+            if (plist && r->ploff != kNoList && r->ploff + plist_window >= ahead) side_parent_list(x, k, r);
+            else if (use_bm) side_bitmap(x, k, r);
+            else side_list(x, k, r);
+        }
+    }
+    // the parent's kept rows (still in the ring) are the domain: only the added item is probed there
+    void side_parent_list(ExpSet& x, uint32_t k, const Rule* r) {
+        Side& sd = x.h_sides[k];
+        x.h_wave[k + 1] =
+            x.h_wave[k] + std::clamp<uint64_t>((uint64_t(r->pn) + kn.pl_spb - 1) / kn.pl_spb, 1, kn.grid.expand);
+        x.h_drv[k + 1] = x.h_drv[k];
+        sd.drv = 0;
+        sd.lmode = 2;
+        sd.pc = r->pc;
+        sd.pleft = r->pleft ? 1u : 0u;
+        sd.pn = r->pn;
+        sd.pl = r->ploff % acap;
+    }
+    // bitmap path: row blocks sized by the expected domain (about twice the rule's support: sids
+    // holding X u Y in either order), exp_spb sids per block; the domain list holds at most the
+    // support of the rarest item of X u Y
+    void side_bitmap(ExpSet& x, uint32_t k, const Rule* r) {
+        Side& sd = x.h_sides[k];
+        x.h_wave[k + 1] =
+            x.h_wave[k] + std::clamp<uint64_t>((2ull * r->sup + kn.exp_spb - 1) / kn.exp_spb, 1, kn.grid.expand);
+        const uint32_t* rx = rp.st.X(r);
+        const uint32_t drv = rarest(rp.st.Y(r), r->ny, rarest(rx, r->nx, rx[0])), cap = sup[drv];
+        x.h_drv[k + 1] = x.h_drv[k] + cap;
+        sd.drv = drv;
+        sd.lmode = kn.dom_mode == 2 || (kn.dom_mode == 0 && uint64_t(cap) * 4 < d->NW) ? 1u : 0u;
+    }
+    // list path: one wave per sid of the driver list: the rarest item of X (expandL needs all
+    // of sids(X)), else of X u Y
+    void side_list(ExpSet& x, uint32_t k, const Rule* r) {
+        const uint32_t* rx = rp.st.X(r);
+        uint32_t drv = rarest(rx, r->nx, rx[0]);
+        if (!r->expandLR) {
+            const uint32_t dxy = rarest(rp.st.Y(r), r->ny, drv);
+            x.drv_in_x[k] = dxy == drv;  // (X and Y share no item)
+            drv = dxy;
+        }
+        x.h_drv[k] = voff[drv];
+        x.h_wave[k + 1] = x.h_wave[k] + (voff[drv + 1] - voff[drv]);
+    }
+    // the slots' kept-row lists at the ring's head, each at most the rule's support
+    void reserve_ring(ExpSet& x, const Rule* const* bp, uint32_t nb) {
+        x.kmono.assign(nb, kNoList);
+        x.amin = kNoList;
+        for (uint32_t k = 0; k < nb; ++k)
+            if (x.h_sides[k].lmode == 2) x.amin = std::min(x.amin, bp[k]->ploff);
+        if (!plist || !acap) return;
+        uint64_t need = 0;
+        for (uint32_t k = 0; k < nb; ++k) need += bp[k]->sup;
+        // (the head skips to the ring's start when a list would wrap)
+        const uint64_t at = ahead % acap + need > acap ? ahead + acap - ahead % acap : ahead;
+        // a launch never overwrites the parent lists its own slots read (x.amin): it keeps
+        // no lists then (only a parent window wider than the default can come this close)
+        const bool own_ok = x.amin == kNoList || x.amin + acap >= at + need;
+        if (!need || need > acap / (4 * uint64_t(kn.nsets)) || !own_ok) return;
+        ahead = at;
+        // positions below ahead + need - acap are overwritten now: a set still in flight
+        // that reads or writes one of them is waited for first
+        for (int xi = 0; xi < kn.nsets; ++xi) {
+            ExpSet& o = xs[xi];
+            if (&o != &x && o.busy && o.amin != kNoList && o.amin + acap < ahead + need) {
+                // its kernels completed is all the ring needs (its results are taken in at
+                // their turn: a finish here would be a rank-local collective when sharded)
+                FSM_HIP(hipEventSynchronize(o.ev[5]));
+                o.amin = kNoList;
+                ++c.ring_waits;
+            }
+        }
+        x.amin = std::min(x.amin, ahead);
+        for (uint32_t k = 0; k < nb; ++k) {
+            x.h_sides[k].ko = ahead % acap;
+            x.h_sides[k].kb = bp[k]->sup;
+            x.kmono[k] = ahead;
+            ahead += bp[k]->sup;
+        }
+    }
+    // partial rows over budget: the budget is shared in proportion to the slots' expected
+    // domains (the launch lasts as long as its largest slot's blocks), at least one block each
+    void fit_blocks(ExpSet& x, uint32_t nb) {
+        uint64_t* wave_off = x.h_wave;
+        if (!use_bm || wave_off[nb] <= max_blocks) return;
+        const uint64_t tot = wave_off[nb];
+        uint64_t prev = 0;  // the original prefix at k
+        for (uint32_t k = 0; k < nb; ++k) {
+            const uint64_t n0 = wave_off[k + 1] - prev;
+            prev = wave_off[k + 1];
+            wave_off[k + 1] = wave_off[k] + std::max<uint64_t>(1, n0 * (max_blocks - nb) / tot);
+        }
+    }
+    // the launch on the set's own stream, its completion in ev[5]
+    void enqueue(ExpSet& x, uint32_t nb) {
+        const hipStream_t xst = x.st;
+        // the descriptors by a copy kernel on the set's stream (reading the mapped staging over PCIe:
+        // an SDMA copy would cost the launch's first kernel a cross-engine wait)
+        static_assert(sizeof(Side) % 4 == 0, "Side: whole words");
+        copy_from_mapped(x.d_stage.p, x.stage->dev, 2 * size_t(B + 1) * 8 + size_t(nb) * sizeof(Side), xst);
+        x.timed = nb && c.launches % kn.time_every == 0;  // every 16th launch is timed (events cost host time)
+        if (nb) {  // (a rank may get no slot of a small sharded batch)
+            if (use_bm) enqueue_bitmap(x, nb, xst);
+            else enqueue_list(x, nb, xst);
+        }
+        if (x.timed) FSM_HIP(hipEventRecord(x.ev[4], xst));
+        FSM_HIP(hipEventRecord(x.ev[5], xst));
+        x.busy = true;
+        ++c.launches;
+    }
+    void enqueue_bitmap(ExpSet& x, uint32_t nb, hipStream_t xst) {
+        const ExpGeo geo{K, KP, uint32_t(x.h_wave[nb]), rp.minsup};
+        if (x.alive_t != rp.minsup) {  // minsup rose: the kids below it stop counting
+            hipLaunchKernelGGL(k_alive, dim3(unsigned(((K + 15) / 16 + kBlock - 1) / kBlock)), dim3(kBlock), 0, xst,
+                               d_ksup.as<uint32_t>(), K, rp.minsup, x.alive.as<uint32_t>());
+            FSM_LAUNCHED("k_alive", xst);
+            x.alive_t = rp.minsup;
+        }
+        if (x.timed) FSM_HIP(hipEventRecord(x.ev[0], xst));
+        bool any_dom = false;  // (every slot on its parent's kept rows: no domain kernel)
+        for (uint32_t k = 0; k < nb && !any_dom; ++k) any_dom = x.h_sides[k].lmode != 2;
+        if (any_dom) {
+            hipLaunchKernelGGL(k_exp_domain, dim3((d->NW + kDomWords - 1) / kDomWords, nb), dim3(kDomThreads),
+                               0, xst, x.d_sides, d->bm.as<uint32_t>(), d->NW, x.d_drv, x.dom.as<uint32_t>(),
+                               x.ctl.as<ExpCtl>(), d->vert_off.as<uint64_t>(), d->vert_sid.as<uint32_t>());
+            FSM_LAUNCHED("k_exp_domain", xst);
+        }
+        if (x.timed) FSM_HIP(hipEventRecord(x.ev[1], xst));
+        hipLaunchKernelGGL(k_exp_rows, dim3(unsigned(x.h_wave[nb]), P), dim3(kXBlock), xlds, xst, x.d_sides,
+                           x.d_wave, nb, x.d_drv, x.dom.as<uint32_t>(), k_off.as<uint32_t>(), k_ent.as<uint2>(),
+                           d_kidof.as<uint32_t>(), x.alive.as<uint32_t>(), geo, x.part.as<uint32_t>(),
+                           x.ctl.as<ExpCtl>(), x.d_ndlw.as<uint32_t>(),
+                           DomProbe{d->bm.as<uint32_t>(), d->NW, d->NW / 4, d_rdir.as<uint32_t>(),
+                                    d_kvoff.as<uint32_t>(), d_vfl.as<uint2>()},
+                           arena.as<uint4>());
+        FSM_LAUNCHED("k_exp_rows", xst);
+        if (x.timed) FSM_HIP(hipEventRecord(x.ev[2], xst));
+        hipLaunchKernelGGL(k_expand_reduce, dim3(kn.grid.collect, nb, P), dim3(kBlock), 0, xst, x.part.as<uint32_t>(),
+                           x.d_wave, geo, d_kept.as<uint32_t>(), x.ctl.as<ExpCtl>(), x.d_rec, ecap,
+                           x.d_dlw.as<uint4>(), x.d_ndlw.as<uint32_t>(), x.d_rcnt, x.d_sides, memo);
+        FSM_LAUNCHED("k_expand_reduce", xst);
+        if (x.timed) FSM_HIP(hipEventRecord(x.ev[3], xst));
+        hipLaunchKernelGGL(k_dl, dim3(kn.grid.dl), dim3(kBlock), 0, xst, x.d_sides, d->bm.as<uint32_t>(),
+                           d->NW, d->vert_off.as<uint64_t>(), d->vert_sid.as<uint32_t>(), x.d_dlw.as<uint4>(),
+                           x.d_ndlw.as<uint32_t>(), x.d_rec, ecap, x.ctl.as<ExpCtl>(), x.d_hdr, nb, memo);
+        FSM_LAUNCHED("k_dl", xst);
+    }
+    void enqueue_list(ExpSet& x, uint32_t nb, hipStream_t xst) {
+        if (x.timed) FSM_HIP(hipEventRecord(x.ev[0], xst));
+        const uint64_t waves = x.h_wave[nb];
+        if (waves) {
+            hipLaunchKernelGGL(k_expand, dim3(unsigned((waves * 64 + kBlock - 1) / kBlock)), dim3(kBlock), 0, xst,
+                               x.d_sides, x.d_drv, x.d_wave, nb,
+                               d->vert_sid.as<uint32_t>(), k_off.as<uint32_t>(), k_item.as<uint32_t>(),
+                               k_first.as<uint32_t>(), k_last.as<uint32_t>(), U, x.TL.as<uint32_t>(),
+                               x.DL.as<uint32_t>(), x.TR.as<uint32_t>(), x.seen.as<uint32_t>(),
+                               x.list.as<uint32_t>(), x.ctl.as<ExpCtl>(), d_sup.as<uint32_t>(), rp.minsup);
+            FSM_LAUNCHED("k_expand", xst);
+        }
+        if (x.timed) FSM_HIP(hipEventRecord(x.ev[1], xst));
+        if (x.timed) FSM_HIP(hipEventRecord(x.ev[2], xst));
+        hipLaunchKernelGGL(k_expand_collect, dim3(kn.grid.collect, nb), dim3(kBlock), 0, xst, x.TL.as<uint32_t>(),
+                           x.DL.as<uint32_t>(), x.TR.as<uint32_t>(), x.seen.as<uint32_t>(), x.list.as<uint32_t>(),
+                           x.ctl.as<ExpCtl>(), U, rp.minsup, x.d_rec, ecap);
+        FSM_LAUNCHED("k_expand_collect", xst);
+        if (x.timed) FSM_HIP(hipEventRecord(x.ev[3], xst));
+        hipLaunchKernelGGL(k_publish, dim3(1), dim3(kBlock), 0, xst, x.ctl.as<ExpCtl>(), x.d_hdr, nb);
+        FSM_LAUNCHED("k_publish", xst);
+    }
+
+    // ---------------- finish
+    // Take in the results of set x (waits for its launch): records sorted into the
+    // cache, and its batch queued for child speculation.
+    void finish(ExpSet& x) {
+        const double tw0 = now_ms();
+        FSM_HIP(hipEventSynchronize(x.ev[5]));
+        const double tw1 = now_ms();
+        c.wait_ms += tw1 - tw0;
+        x.busy = false;
+        take_timing(x);
+        const uint32_t nb = x.lz - x.la;  // the slots expanded here (slot sharding: this rank's share)
+        if (use_bm && nb) {
+            c.exp_part_bytes += int64_t(x.blocks * row_bytes);
+            c.seg[1].bytes += int64_t(x.blocks * row_bytes);  // the partial rows the row kernel writes
+        }
+        uint64_t nout_all = 0;
+        ctx->stats.rank_units += int64_t(nb);
+        for (uint32_t k = 0; k < nb; ++k) nout_all += take_slot(x, k);
+        if (x.sharded) gather_slots(x, nb);
+        c.seg[2].bytes += int64_t(nout_all * sizeof(ExpRec));
+        x.timed = false;
+        spec_todo.emplace_back(std::move(x.batch), x.depth);
+        x.batch.clear();
+        c.post_ms += now_ms() - tw1;
+    }
+    void take_timing(const ExpSet& x) {
+        for (int q = 0; q < 4; ++q) {
+            float ms = 0;
+            if (x.timed && hipEventElapsedTime(&ms, x.ev[q], x.ev[q + 1]) == hipSuccess) {
+                c.seg[q].ms += ms;
+                c.seg[q].timed += 1;
+            }
+            c.seg[q].n += 1;
+        }
+    }
+    // slot k of this rank's share: its accounting, and its records into the rule's results
+    // (unless the rule was dropped meanwhile).  Returns the records the kernels wrote
+    uint32_t take_slot(ExpSet& x, uint32_t k) {
+        Rule* r = x.batch[x.la + k];
+        const ExpHdr h = x.h_hdr[k];
+        if (use_bm) {
+            // own bytes: domain = the |X|+|Y| bitmap operands + 4 B written per domain sid;
+            // rows = per domain sid its id and row bounds (12 B) and |X u Y| probes (rank
+            // directory 4 B + bitmap words 16 B + vertical entry 8 B), or per parent row 16 B
+            // and one probe (plist), + 8 B per entry walked + 16 B per kept row written
+            const bool pm = x.h_sides[k].lmode == 2;
+            const uint64_t bmb = pm ? 0ull : uint64_t(r->nx + r->ny) * d->NW * 4;
+            const uint64_t ndom = pm ? r->pn : h.nsid;
+            c.exp_domain += ndom;
+            c.exp_entries += h.nent;
+            c.exp_hold += h.nhold;
+            c.exp_walk += h.nwalk;
+            c.exp_plist += pm ? 1 : 0;
+            c.exp_bitmap_bytes += int64_t(bmb);
+            c.seg[0].bytes += int64_t(bmb + 4ull * (pm ? 0ull : h.nsid));
+            c.seg[1].bytes += int64_t(8ull * h.nwalk + (pm ? 44ull : 12ull + 28ull * (r->nx + r->ny)) * ndom +
+                                      (x.kmono[k] != kNoList ? 16ull * h.ln : 0ull));
+            // SURVEY: N/8 B per sid-bitmap operand; 4 B token + 4 B first/last per position of
+            // every sequence where the rule holds (the reference scans each of them whole)
+            c.seg[0].survey += int64_t(bmb);
+            c.seg[1].survey += int64_t(8ull * h.nent);
+            // the rule's kept rows (more than its support: the list was cut, none kept)
+            r->loff = x.kmono[k] != kNoList && h.ln <= x.h_sides[k].kb ? x.kmono[k] : kNoList;
+            r->ln = h.ln;
+        }
+        if (h.nout > ecap) throw Error(FSM_ELIMIT, "TSR: expansion candidate buffer overflow");
+        if (!use_bm && x.drv_in_x[k] && h.nx != r->nX)
+            throw Error(FSM_EDEVICE, "TSR: |sids(X)| mismatch in expansion (" + std::to_string(h.nx) + " vs " +
+                                         std::to_string(r->nX) + ")");
+        r->inset = -1;
+        if (r->dropped) return h.nout;  // a speculated child its parent's commit did not register
+        ExpResult& res = results.get(r);
+        const ExpRec* rec = x.h_rec + size_t(k) * ecap;
+        if (use_bm) {  // the reduce blocks' kid ranges, in kid (= item) order
+            res.recs.clear();
+            res.recs.reserve(h.nout);
+            const uint32_t* rc = x.h_rcnt + size_t(k) * P * kn.grid.collect;
+            const uint32_t q = (KP + kn.grid.collect - 1) / kn.grid.collect;
+            for (uint32_t p = 0; p < P; ++p)
+                for (uint32_t g = 0; g < kn.grid.collect; ++g) {
+                    const ExpRec* r0 = rec + size_t(p) * KP + size_t(g) * q;
+                    res.recs.insert(res.recs.end(), r0, r0 + rc[p * kn.grid.collect + g]);
+                }
+        } else {
+            res.recs.assign(rec, rec + h.nout);
+            std::sort(res.recs.begin(), res.recs.end(), [](const ExpRec& a, const ExpRec& b) { return a.c < b.c; });
+        }
+        return h.nout;
+    }
+    // a sharded launch: every rank's slots, (nsid, nent, nrec, records) per slot of its share,
+    // gathered once per launch (the failure agreement rides along); the replay then goes on
+    // alike on every rank
+    void gather_slots(ExpSet& x, uint32_t nb) {
+        std::vector<uint8_t> mine;
+        auto put = [&](const void* p, size_t n) {
+            const uint8_t* b = static_cast<const uint8_t*>(p);
+            mine.insert(mine.end(), b, b + n);
+        };
+        for (uint32_t k = 0; k < nb; ++k) {
+            Rule* r = x.batch[x.la + k];
+            const ExpHdr h = x.h_hdr[k];
+            const uint32_t nrec = r->dropped || r->res < 0 ? 0u : uint32_t(results.of(r).recs.size());
+            const uint32_t hd[3] = {h.nsid, h.nent, nrec};
+            put(hd, sizeof(hd));
+            if (nrec) put(results.of(r).recs.data(), nrec * sizeof(ExpRec));
+        }
+        std::vector<size_t> sizes;
+        const std::vector<uint8_t> all = comm->gather_blobs(mine, sizes, s, &agr);
+        // the ranks' blobs hold their contiguous slot ranges, in rank and slot order
+        size_t at = 0;
+        uint32_t k = 0;
+        for (int q = 0; q < R; ++q) {
+            const size_t end = at + sizes[size_t(q)];
+            for (; k < x.batch.size() && at < end; ++k) {
+                uint32_t hd[3];
+                std::memcpy(hd, all.data() + at, sizeof(hd));
+                at += sizeof(hd);
+                Rule* r = x.batch[k];
+                if (q != comm->rank()) {
+                    c.exp_domain += hd[0];
+                    c.exp_entries += hd[1];
+                    r->inset = -1;
+                    if (!r->dropped) {
+                        ExpResult& res = results.get(r);
+                        res.recs.resize(hd[2]);
+                        if (hd[2]) std::memcpy(res.recs.data(), all.data() + at, hd[2] * sizeof(ExpRec));
+                    }
+                }
+                at += size_t(hd[2]) * sizeof(ExpRec);
+            }
+        }
+        if (at != all.size()) throw Error(FSM_EDEVICE, "TSR: sharded expansion results out of step");
+    }
+
+    // ---------------- replay
+    // a speculated child that its parent's commit did not register: drop its
+    // results (cached, or marked so that an in-flight launch's are discarded) and,
+    // recursively, those of its own speculated children
+    void drop_spec(Rule* x) {
+        x->dropped = true;
+        c.spec_waste += x->spec;
+        if (x->res < 0) return;
+        std::vector<Rule*> kids;
+        {
+            const ExpResult& e = results.of(x);
+            for (Rule* k : e.preL) if (k) kids.push_back(k);
+            for (Rule* k : e.preR) if (k) kids.push_back(k);
+        }
+        results.release(x);
+        for (Rule* k : kids) drop_spec(k);
+    }
+    // one half of r's commit.  kLeft: expandL, X u {c} => Y (supports tl, children preL);
+    // else expandR, X => Y u {c} (tr, preR).  A child speculated ahead (pre) is registered
+    // as it is, or dropped when it fell below minsup
+    template <bool kLeft> void commit_side(Rule* r, ExpResult& res, bool pre) {
+        const std::vector<Rule*>& prebuilt = kLeft ? res.preL : res.preR;
+        for (size_t i = 0; i < res.recs.size(); ++i) {
+            const ExpRec& e = res.recs[i];
+            const uint32_t esup = kLeft ? e.tl : e.tr;
+            Rule* sp = pre ? prebuilt[i] : nullptr;
+            if (esup == 0 || esup < rp.minsup) {
+                if (sp) drop_spec(sp);
+                continue;
+            }
+            take(sp ? sp : (kLeft ? rp.derive(r, e.c, kNone, e.tl, e.dl) : rp.derive(r, kNone, e.c, e.tr, r->nX)), kLeft);
+        }
+    }
+    void commit(Rule* r, ExpResult& res) {
+        const bool pre = !res.preL.empty();
+        c.expansions += r->expandLR ? 2 : 1;
+        if (ctx->opts.verbose && now_ms() - c.last_log_ms > 20000.0 && (c.last_log_ms = now_ms()) > 0)
+            std::fprintf(stderr, "[fsm tsr] %lld expansions, minsup %u, candidates %zu, rules %zu, %.0f ms\n",
+                         (long long)c.expansions, rp.minsup, rp.cand.size(), rp.krules.size(), now_ms() - t0);
+        if (r->expandLR) commit_side<true>(r, res, pre);
+        commit_side<false>(r, res, pre);
+    }
+    // Child speculation: when a launch finishes, the children of its rules that
+    // rank at or above the lowest pending rule (sup >= T) are the ones whose
+    // registration would force the next launch (a fresh rule outranking the
+    // pending front).  They are created now, exactly as their parent's commit
+    // would create them, and expanded in a follow-up launch (a few levels deep)
+    // while the host commits; the commit then registers the pre-built rule
+    // (results cached or in flight) instead of deriving it again.
+    // speculate(): the next level of one finished launch's batch
+    void speculate(const std::vector<Rule*>& level, int depth) {
+        if (!kn.spec_on || depth >= kn.spec_depth || level.empty()) return;
+        uint32_t T = 0xFFFFFFFFu;
+        for (Rule* x : level) T = std::min(T, x->sup);
+        if (!pending.empty()) T = std::min(T, pending.min_sup());
+        T = std::max(uint32_t(double(T) * kn.spec_frac), rp.minsup);
+        std::vector<Rule*> next;
+        for (Rule* x : level) {
+            if (x->res < 0) continue;  // committed already, or dropped
+            ExpResult& res = results.of(x);
+            const size_t n = res.recs.size();
+            res.preL.assign(n, nullptr);
+            res.preR.assign(n, nullptr);
+            auto ahead_of_commit = [&](bool left, const ExpRec& e, Rule*& slot) {
+                slot = left ? rp.derive(x, e.c, kNone, e.tl, e.dl) : rp.derive(x, kNone, e.c, e.tr, x->nX);
+                slot->expandLR = left;
+                slot->spec = true;
+                next.push_back(slot);
+            };
+            for (size_t i = 0; i < n && next.size() < size_t(spec_max); ++i) {
+                const ExpRec& e = res.recs[i];
+                if (x->expandLR && e.tl >= T) ahead_of_commit(true, e, res.preL[i]);
+                if (e.tr >= T && next.size() < size_t(spec_max)) ahead_of_commit(false, e, res.preR[i]);
+            }
+        }
+        c.spec_made += int64_t(next.size());
+        for (size_t a = 0; a < next.size(); a += size_t(B)) {
+            const std::vector<Rule*> part(next.begin() + a, next.begin() + std::min(next.size(), a + size_t(B)));
+            launch(part, depth + 1);
+            ++c.spec_launches;
+        }
+    }
+    // the next rule to commit is the larger of the heap top and the pending front; one with
+    // neither results nor a launch is expanded together with the next heap rules
+    void replay() {
+        std::vector<Rule*> batch, popped;  // popped: one pop loop's rules (a run of `pending`)
+        for (;;) {
+            // children of finished launches first (their launches overlap the commits below)
+            while (!spec_todo.empty()) {
+                std::vector<std::pair<std::vector<Rule*>, int>> todo;
+                todo.swap(spec_todo);
+                for (auto& [lvl, dp] : todo) speculate(lvl, dp);
+            }
+            const bool have_h = !rp.cand.empty(), have_p = !pending.empty();
+            if (!have_h && !have_p) break;
+            const bool from_p = have_p && (!have_h || rule_cmp(rp.st, pending.front(), rp.cand.top().r) > 0);
+            Rule* r = from_p ? pending.front() : rp.cand.top().r;
+            if (r->sup < rp.minsup) break;
+            if (r->res < 0 && r->inset >= 0) {  // expanding on the GPU: take its launch in, then decide again
+                finish(xs[r->inset]);
+                continue;
+            }
+            if (r->res >= 0) {  // results at hand: commit now
+                if (from_p) pending.pop();
+                else rp.cand.pop();
+                // (the host-time split is taken only when verbose: a clock read costs as much as a commit)
+                const double tc0 = ctx->opts.verbose ? now_ms() : 0.0;
+                commit(r, results.of(r));
+                c.spec_hit += r->spec;
+                if (r->res >= 0) results.release(r);
+                if (ctx->opts.verbose) c.commit_ms += now_ms() - tc0;
+                results.sweep(rp.minsup);
+                continue;
+            }
+            if (from_p) throw Error(FSM_EDEVICE, "TSR: a pending rule has neither results nor a launch");
+            const double tp0 = now_ms();
+            batch.clear();
+            popped.clear();
+            while (batch.size() < size_t(B) && !rp.cand.empty() && uint32_t(rp.cand.top().k1 >> 32) >= rp.minsup) {
+                Rule* x = rp.cand.top().r;
+                rp.cand.pop();
+                popped.push_back(x);
+                if (x->res < 0 && x->inset < 0) batch.push_back(x);  // else already expanded by speculation
+            }
+            pending.add(popped);
+            c.pop_ms += now_ms() - tp0;
+            launch(batch, 0);
+            c.spec_pushback += int64_t(batch.size()) - 1;
+        }
+        for (int xi = 0; xi < kn.nsets; ++xi)  // speculation still in flight when the replay ended
+            if (xs[xi].busy) finish(xs[xi]);
+    }
+
+    // ---------------- results
+    void print_summary() const {
+        if (!ctx->opts.verbose) return;
+        std::fprintf(stderr,
+                     "[fsm tsr] expansions %lld in %lld launches (%lld rules expanded, %lld pushed back), %.0f ms waiting on the "
+                     "GPU; host: %.0f ms launch prep (%.0f descriptors), %.0f ms result intake, %.0f ms commit, %.0f ms batch pops; %zu rules "
+                     "made\n",
+                     (long long)c.expansions, (long long)c.launches, (long long)c.gpu_rules, (long long)c.spec_pushback,
+                     c.wait_ms, c.prep_ms, c.fill_ms, c.post_ms, c.commit_ms, c.pop_ms, rp.st.size());
+        std::fprintf(stderr, "[fsm tsr] child speculation: %lld rules in %lld launches (%lld committed, %lld dropped); partial rows %.1f MB; domain sids "
+                     "%lld (row entries %lld), rows where the rule holds %lld, row entries walked %lld; "
+                     "rules on their parent's kept rows %lld (ring: %llu entries written, %lld early finishes); candidates sorted %zu, popped %zu\n",
+                     (long long)c.spec_made, (long long)c.spec_launches, (long long)c.spec_hit, (long long)c.spec_waste,
+                     double(c.exp_part_bytes) / 1e6, (long long)c.exp_domain, (long long)c.exp_entries,
+                     (long long)c.exp_hold, (long long)c.exp_walk, (long long)c.exp_plist, (unsigned long long)ahead,
+                     (long long)c.ring_waits, rp.cand.n_sorted, rp.cand.n_popped);
+    }
+    // result = kRules, lowest first
+    fsm_rules* write_rules() {
+        std::vector<const Rule*> res;
+        while (!rp.krules.empty()) {
+            res.push_back(rp.krules.top().r);
+            rp.krules.pop();
+        }
+        const size_t n = res.size();
+        size_t na = 0, nc = 0;
+        for (const Rule* r : res) { na += r->nx; nc += r->ny; }
+        MallocArr<int32_t> support(n), ante(na), cons(nc);
+        MallocArr<double> confidence(n);
+        MallocArr<int64_t> ante_off(n + 1), cons_off(n + 1);
+        ante_off[0] = cons_off[0] = 0;
+        for (size_t q = 0; q < n; ++q) {
+            const Rule* r = res[q];
+            support[q] = int32_t(r->sup);
+            confidence[q] = r->conf;
+            const uint32_t *rx = rp.st.X(r), *ry = rp.st.Y(r);
+            for (uint32_t x = 0; x < r->nx; ++x) ante[size_t(ante_off[q]) + x] = db->tsr.item_val[rx[x]];
+            for (uint32_t x = 0; x < r->ny; ++x) cons[size_t(cons_off[q]) + x] = db->tsr.item_val[ry[x]];
+            ante_off[q + 1] = ante_off[q] + int64_t(r->nx);
+            cons_off[q + 1] = cons_off[q] + int64_t(r->ny);
+        }
+        auto* o = static_cast<fsm_rules*>(std::calloc(1, sizeof(fsm_rules)));
+        if (!o) throw Error(FSM_ENOMEM, "calloc failed");
+        o->n = int64_t(n);
+        o->total = d->N;
+        o->final_minsup = int32_t(rp.minsup);
+        o->support = support.release();
+        o->confidence = confidence.release();
+        o->ante_off = ante_off.release();
+        o->cons_off = cons_off.release();
+        o->ante = ante.release();
+        o->cons = cons.release();
+        return o;
+    }
+    void write_stats(int64_t n_rules) {
+        ctx->kstats.clear();
+        for (int q = 0; q < 4; ++q) {
+            if (!seg_name[q][0]) continue;
+            const TsrCounters::Seg& sg = c.seg[q];
+            fsm_kernel_stat k{};
+            std::snprintf(k.name, sizeof(k.name), "%s", seg_name[q]);
+            k.launches = sg.n;
+            k.ms = sg.timed ? sg.ms * double(sg.n) / double(sg.timed) : 0.0;  // sampled, scaled
+            k.alg_bytes = sg.bytes;
+            k.survey_bytes = sg.survey;
+            ctx->kstats.push_back(k);
+        }
+        ctx->stats.tsr_ring_waits = c.ring_waits;
+        ctx->stats.exp_domain = c.exp_domain;
+        ctx->stats.exp_entries = c.exp_entries;
+        ctx->stats.exp_bitmap_bytes = c.exp_bitmap_bytes;
+        ctx->stats.expansions = c.expansions;
+        ctx->stats.rules = n_rules;
+        ctx->stats.ms_f2 = t1 - t0;             // pair phase
+        ctx->stats.ms_lattice = now_ms() - t1;  // expansions
+        ctx->stats.ms_count_kernel = c.wait_ms;  // of which: waiting for the expansion kernels
+        ctx->stats.count_launches = c.launches;
+        ctx->stats.ms_mine = now_ms() - t0;
+    }
+};
+
 }  // namespace
 
 void tsr_upload(fsm_ctx* ctx, fsm_db* db) {
@@ -1580,1210 +2911,15 @@ void tsr_release(fsm_db* db) {
 
 void tsr_mine(fsm_ctx* ctx, fsm_db* db, int32_t k, double minconf, fsm_rules** out) {
     const double t0 = now_ms();
-    TsrDevDB* d = db->tsr_dev;
-    hipStream_t s = ctx->stream;
-    const uint32_t U = uint32_t(d->U);
-    Replay rp{k, minconf};
-    rp.xin.init(U);
-    std::vector<uint64_t> voff(size_t(U) + 1);
-    FSM_HIP(hipMemcpyAsync(voff.data(), d->vert_off.p, (size_t(U) + 1) * 8, hipMemcpyDeviceToHost, s));
-    DevBuf d_sup(size_t(std::max<uint32_t>(U, 1)) * 4);
-    FSM_HIP(hipMemcpyAsync(d_sup.p, d->sup.data(), size_t(U) * 4, hipMemcpyHostToDevice, s));
-    FSM_HIP(hipStreamSynchronize(s));
-    const std::vector<uint32_t>& sup = d->sup;
-
-    // ---------------- pair phase (i ascending, j > i; IJ then JI)
-    // nranks > 1: each rank counts the pairs of its own sequence range; the candidate
-    // keys are exchanged and their partial counts summed.  The
-    // expansions then run on every rank alike (replicated, no exchange).  A failure
-    // on one rank is agreed on before each collective, so no peer is left blocked.
-    Comm* comm = ctx->comm;
-    const bool shard = comm && comm->nranks() > 1;
-    Agreement agr;
-    agr.comm = shard ? comm : nullptr;
-    agr.what = "TSR";
-    const int R = shard ? comm->nranks() : 1;
-    const uint32_t slo = shard ? uint32_t(uint64_t(d->N) * uint64_t(comm->rank()) / uint64_t(R)) : 0u;
-    const uint32_t shi = shard ? uint32_t(uint64_t(d->N) * uint64_t(comm->rank() + 1) / uint64_t(R))
-                               : uint32_t(d->N);
-    uint64_t rp_pair_exchanged = 0;  // union keys exchanged (verbose)
-    uint32_t nb_items = 16;
-    // the batch grows while a batch's candidate records stay below pair_recs and
-    // shrinks above 4 x pair_recs (FSM_TSR_PAIR_RECS lowers it: test hook for the
-    // sharded batch agreement)
-    const uint64_t pair_recs = [] {
-        const char* v = std::getenv("FSM_TSR_PAIR_RECS");
-        return v ? std::clamp<uint64_t>(std::strtoull(v, nullptr, 10), 1, uint64_t(1) << 30) : uint64_t(1) << 20;
-    }();
-    const uint64_t scr_cap_items = std::max<uint64_t>(1, (uint64_t(256) << 20) / (uint64_t(std::max<uint32_t>(U, 1)) * 8));
-    DevBuf scr;
-    uint64_t scr_items = 0;
-    std::vector<PairRec> recs;
-    for (uint32_t a = 0; a < U;) {
-        const uint32_t t = rp.minsup;
-        const uint32_t nb = uint32_t(std::min<uint64_t>({uint64_t(nb_items), uint64_t(U - a), scr_cap_items}));
-        const uint32_t b = a + nb;
-        // compaction threshold: t, or ceil(t / R) for a rank's partial counts (a pair whose
-        // total reaches t has a partial >= t / R on some rank)
-        const uint32_t tq = shard ? (t + uint32_t(R) - 1) / uint32_t(R) : t;
-        const unsigned grid = unsigned((uint64_t(nb) * 64 + kBlock - 1) / kBlock);
-        std::vector<uint64_t> hoff(size_t(nb) + 1, 0);
-        std::vector<PairRec> mine;
-        uint64_t nrec = 0;
-        // this rank's counts of the batch (rank-local work: deferred on failure when sharded)
-        agr.run([&] {
-            if (shard) agr.maybe_inject("pairs");
-            if (scr_items < nb) {
-                scr.alloc(uint64_t(nb) * U * 8);
-                FSM_HIP(hipMemsetAsync(scr.p, 0, uint64_t(nb) * U * 8, s));
-                scr_items = nb;
-            }
-            const uint64_t v0 = voff[a], v1 = voff[b];
-            if (v1 > v0) {
-                hipLaunchKernelGGL(k_pairs, dim3(unsigned((v1 - v0 + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
-                                   d->vert_sid.as<uint32_t>(), d->vert_item.as<uint32_t>(), v0, v1, a, U, t, slo, shi,
-                                   d_sup.as<uint32_t>(), d->row_off.as<uint32_t>(), d->item.as<uint32_t>(),
-                                   d->first.as<uint32_t>(), d->last.as<uint32_t>(), scr.as<uint32_t>());
-                FSM_LAUNCHED("k_pairs", s);
-            }
-            DevBuf rowcnt(size_t(nb) * 4 + 4), rowoff((size_t(nb) + 1) * 8);
-            hipLaunchKernelGGL(k_pairs_compact, dim3(grid), dim3(kBlock), 0, s, scr.as<uint32_t>(), a, nb, U, tq,
-                               rowcnt.as<uint32_t>(), rowoff.as<uint64_t>(), (PairRec*)nullptr, 0);
-            FSM_LAUNCHED("k_pairs_compact", s);
-            scan_exclusive(rowcnt.as<uint32_t>(), rowoff.as<uint64_t>(), nb, s);
-            FSM_HIP(hipMemcpyAsync(hoff.data(), rowoff.p, (size_t(nb) + 1) * 8, hipMemcpyDeviceToHost, s));
-            FSM_HIP(hipStreamSynchronize(s));
-            nrec = hoff[nb];
-            DevBuf d_recs(std::max<uint64_t>(nrec, 1) * sizeof(PairRec));
-            // unsharded: the compaction also re-zeroes the counters it visits; sharded: the
-            // counters are read again for the union's partials
-            hipLaunchKernelGGL(k_pairs_compact, dim3(grid), dim3(kBlock), 0, s, scr.as<uint32_t>(), a, nb, U, tq,
-                               rowcnt.as<uint32_t>(), rowoff.as<uint64_t>(), d_recs.as<PairRec>(), shard ? 0 : 1);
-            FSM_LAUNCHED("k_pairs_compact", s);
-            std::vector<PairRec>& dst = shard ? mine : recs;
-            dst.resize(nrec);
-            if (nrec) FSM_HIP(hipMemcpyAsync(dst.data(), d_recs.p, nrec * sizeof(PairRec), hipMemcpyDeviceToHost, s));
-            FSM_HIP(hipStreamSynchronize(s));
-        });
-        uint64_t nadapt = nrec;  // drives the next batch size (must be alike on every rank)
-        if (shard) {
-            // candidate keys of this rank -> union over ranks -> every rank's partials of
-            // the union summed -> the exact counts, kept at t like the one-rank compaction
-            agr.agree(s);
-            std::vector<uint8_t> blob(mine.size() * 8);
-            for (size_t q = 0; q < mine.size(); ++q) {
-                std::memcpy(blob.data() + q * 8, &mine[q].i, 4);
-                std::memcpy(blob.data() + q * 8 + 4, &mine[q].j, 4);
-            }
-            std::vector<size_t> sizes;
-            const std::vector<uint8_t> all = comm->gather_blobs(blob, sizes, s);
-            std::vector<uint2> keys(all.size() / 8);
-            for (size_t q = 0; q < keys.size(); ++q) std::memcpy(&keys[q], all.data() + q * 8, 8);
-            std::sort(keys.begin(), keys.end(),
-                      [](const uint2& x, const uint2& y) { return x.x != y.x ? x.x < y.x : x.y < y.y; });
-            keys.erase(std::unique(keys.begin(), keys.end(),
-                                   [](const uint2& x, const uint2& y) { return x.x == y.x && x.y == y.y; }),
-                       keys.end());
-            std::vector<uint32_t> part(keys.size() * 2, 0u);
-            agr.run([&] {
-                for (const uint2& kk : keys)  // every rank batched [a, b) alike
-                    if (kk.x < a || kk.x >= b || kk.y >= U)
-                        throw Error(FSM_EDEVICE, "TSR sharded pair phase: exchanged key outside the batch");
-                if (!keys.empty()) {
-                    DevBuf d_keys(keys.size() * 8), d_part(keys.size() * 8);
-                    FSM_HIP(hipMemcpyAsync(d_keys.p, keys.data(), keys.size() * 8, hipMemcpyHostToDevice, s));
-                    hipLaunchKernelGGL(k_pairs_gather, dim3(unsigned((keys.size() + kBlock - 1) / kBlock)),
-                                       dim3(kBlock), 0, s, scr.as<uint32_t>(), a, U, d_keys.as<uint2>(),
-                                       uint32_t(keys.size()), d_part.as<uint32_t>());
-                    FSM_LAUNCHED("k_pairs_gather", s);
-                    FSM_HIP(hipMemcpyAsync(part.data(), d_part.p, keys.size() * 8, hipMemcpyDeviceToHost, s));
-                }
-                FSM_HIP(hipMemsetAsync(scr.p, 0, uint64_t(nb) * U * 8, s));
-                FSM_HIP(hipStreamSynchronize(s));
-            });
-            agr.agree(s);
-            comm->host_allreduce_u32(part.data(), part.size(), s);
-            recs.clear();
-            std::fill(hoff.begin(), hoff.end(), 0);
-            for (size_t q = 0; q < keys.size(); ++q) {
-                const uint32_t ij = part[2 * q], ji = part[2 * q + 1];
-                if (ij < t && ji < t) continue;
-                recs.push_back(PairRec{keys[q].x, keys[q].y, ij, ji});
-                hoff[keys[q].x - a + 1] += 1;
-            }
-            for (uint32_t g = 0; g < nb; ++g) hoff[g + 1] += hoff[g];
-            rp_pair_exchanged += keys.size();
-            nadapt = keys.size();  // the union: the same number on every rank
-        }
-        for (uint32_t g = 0; g < nb; ++g) {
-            const uint32_t i = a + g;
-            if (sup[i] < rp.minsup) continue;
-            for (uint64_t q = hoff[g]; q < hoff[g + 1]; ++q) {
-                const PairRec& pr = recs[q];
-                const uint32_t j = pr.j;
-                if (sup[j] < rp.minsup) continue;
-                if (pr.ij >= rp.minsup) {
-                    Rule* r = rp.derive(nullptr, i, j, pr.ij, sup[i]);
-                    if (r->conf >= minconf) rp.save(r);
-                    rp.reg(r, true);
-                }
-                if (pr.ji >= rp.minsup) {
-                    Rule* r = rp.derive(nullptr, j, i, pr.ji, sup[j]);
-                    if (r->conf >= minconf) rp.save(r);
-                    rp.reg(r, true);
-                }
-            }
-        }
-        if (nadapt < pair_recs) nb_items = std::min<uint32_t>(nb_items * 2, 4096);
-        else if (nadapt > 4 * pair_recs && nb_items > 1) nb_items /= 2;
-        a = b;
-    }
-    scr.release();
-    // The expansions see only the items that can still be in a rule: support >=
-    // the pair phase's minsup, which only rises from here (K "kept" items).
-    std::vector<uint32_t> kept_items;
-    for (uint32_t c = 0; c < U; ++c)
-        if (sup[c] >= rp.minsup) kept_items.push_back(c);
-    const uint32_t K = uint32_t(kept_items.size());
-    const uint64_t N = uint64_t(d->N);
-    // bitmap path: sid bitmaps built, K <= kMaxKids, itemset indexes < 2^16 (packed rows);
-    // FSM_TSR_MAX_KIDS / FSM_TSR_MAX_POS lower both caps (test hooks: the list path, taken up
-    // front or after the rows were packed)
-    const uint32_t max_kids = [] {
-        const char* v = std::getenv("FSM_TSR_MAX_KIDS");
-        return v ? std::min<uint32_t>(uint32_t(std::strtoul(v, nullptr, 10)), kMaxKids) : kMaxKids;
-    }();
-    const uint32_t max_pos = [] {
-        const char* v = std::getenv("FSM_TSR_MAX_POS");
-        return v ? std::min<uint32_t>(uint32_t(std::strtoul(v, nullptr, 10)), 0xFFFFu) : 0xFFFFu;
-    }();
-    bool use_bm = d->bm.p != nullptr && K > 0 && K <= max_kids;
-    std::vector<uint32_t> h_kid_of;  // bitmap path: item -> kid (host copy)
-    DevBuf k_off, k_item, k_first, k_last, k_sup;  // list path rows (SoA)
-    DevBuf k_ent, d_kidof, d_kept, d_ksup;  // bitmap path rows (packed) and kid tables
-    DevBuf d_rdir, d_kvoff, d_vfl;          // bitmap path: rank directories and vertical entries of the kids
-    uint64_t E2 = 0;
-    const unsigned rows_grid = unsigned(std::min<uint64_t>((N * 64 + kBlock - 1) / kBlock, 65536));
-    if (use_bm) {
-        std::vector<uint32_t>& kid_of = h_kid_of;
-        kid_of.assign(U, kNone);
-        std::vector<uint32_t> ksup(K);
-        for (uint32_t q = 0; q < K; ++q) {
-            kid_of[kept_items[q]] = q;
-            ksup[q] = sup[kept_items[q]];
-        }
-        d_kidof.alloc(size_t(std::max<uint32_t>(U, 1)) * 4);
-        d_kept.alloc(size_t(K) * 4);
-        d_ksup.alloc(size_t(K) * 4);
-        FSM_HIP(hipMemcpyAsync(d_kidof.p, kid_of.data(), size_t(U) * 4, hipMemcpyHostToDevice, s));
-        FSM_HIP(hipMemcpyAsync(d_kept.p, kept_items.data(), size_t(K) * 4, hipMemcpyHostToDevice, s));
-        FSM_HIP(hipMemcpyAsync(d_ksup.p, ksup.data(), size_t(K) * 4, hipMemcpyHostToDevice, s));
-        DevBuf rc(std::max<uint64_t>(N, 1) * 4), off64((N + 1) * 8), mpos(4);
-        FSM_HIP(hipMemsetAsync(mpos.p, 0, 4, s));
-        if (N) {
-            hipLaunchKernelGGL(k_rows_pack, dim3(rows_grid), dim3(kBlock), 0, s, d->row_off.as<uint32_t>(),
-                               d->item.as<uint32_t>(), d->first.as<uint32_t>(), d->last.as<uint32_t>(),
-                               d_kidof.as<uint32_t>(), N, rc.as<uint32_t>(), mpos.as<uint32_t>(),
-                               (const uint64_t*)nullptr, (uint2*)nullptr);
-            FSM_LAUNCHED("k_rows_pack", s);
-        }
-        scan_exclusive(rc.as<uint32_t>(), off64.as<uint64_t>(), N, s);
-        uint32_t maxpos = 0;
-        FSM_HIP(hipMemcpyAsync(&E2, off64.as<uint64_t>() + N, 8, hipMemcpyDeviceToHost, s));
-        FSM_HIP(hipMemcpyAsync(&maxpos, mpos.p, 4, hipMemcpyDeviceToHost, s));
-        FSM_HIP(hipStreamSynchronize(s));
-        if (maxpos > max_pos || E2 >= kNone) {
-            use_bm = false;  // an itemset index past 2^16: the list path takes it
-        } else {
-            k_off.alloc((N + 1) * 4);
-            k_ent.alloc(std::max<uint64_t>(E2, 1) * 8);
-            hipLaunchKernelGGL(k_off32, dim3(unsigned(std::min<uint64_t>((N + 256) / 256, 4096))), dim3(256), 0, s,
-                               off64.as<uint64_t>(), N, k_off.as<uint32_t>());
-            FSM_LAUNCHED("k_off32", s);
-            if (N) {
-                hipLaunchKernelGGL(k_rows_pack, dim3(rows_grid), dim3(kBlock), 0, s, d->row_off.as<uint32_t>(),
-                                   d->item.as<uint32_t>(), d->first.as<uint32_t>(), d->last.as<uint32_t>(),
-                                   d_kidof.as<uint32_t>(), N, (uint32_t*)nullptr, (uint32_t*)nullptr,
-                                   off64.as<uint64_t>(), k_ent.as<uint2>());
-                FSM_LAUNCHED("k_rows_pack", s);
-            }
-            // the kept items' rank directories and vertical entries (k_exp_domain's probes)
-            std::vector<uint32_t> kvoff(size_t(K) + 1, 0);
-            for (uint32_t q = 0; q < K; ++q) kvoff[q + 1] = kvoff[q] + ksup[q];
-            if (kvoff[K] != E2) throw Error(FSM_EDEVICE, "TSR: kept row entries differ from the kept supports");
-            d_kvoff.alloc((size_t(K) + 1) * 4);
-            FSM_HIP(hipMemcpyAsync(d_kvoff.p, kvoff.data(), (size_t(K) + 1) * 4, hipMemcpyHostToDevice, s));
-            d_rdir.alloc(std::max<size_t>(size_t(K) * (d->NW / 4) * 4, 4));
-            hipLaunchKernelGGL(k_rank_dir, dim3(K), dim3(kBlock), 0, s, d->bm.as<uint32_t>(), d->NW,
-                               d_kept.as<uint32_t>(), d_rdir.as<uint32_t>());
-            FSM_LAUNCHED("k_rank_dir", s);
-            d_vfl.alloc(std::max<uint64_t>(E2, 1) * 8);
-            if (N) {
-                hipLaunchKernelGGL(k_vfl, dim3(unsigned(std::min<uint64_t>((N + kBlock - 1) / kBlock, 65536))),
-                                   dim3(kBlock), 0, s, k_off.as<uint32_t>(), k_ent.as<uint2>(), uint32_t(N),
-                                   d->bm.as<uint32_t>(), d->NW, d_kept.as<uint32_t>(), d_rdir.as<uint32_t>(),
-                                   d_kvoff.as<uint32_t>(), d_vfl.as<uint2>());
-                FSM_LAUNCHED("k_vfl", s);
-            }
-            FSM_HIP(hipStreamSynchronize(s));
-        }
-    }
-    if (!use_bm) {  // list path: rows restricted to the kept items, SoA with each entry's item support
-        DevBuf rc(std::max<uint64_t>(N, 1) * 4), off64((N + 1) * 8);
-        if (N) {
-            hipLaunchKernelGGL(k_rows_keep, dim3(rows_grid), dim3(kBlock), 0, s, d->row_off.as<uint32_t>(),
-                               d->item.as<uint32_t>(), d->first.as<uint32_t>(), d->last.as<uint32_t>(),
-                               d_sup.as<uint32_t>(), rp.minsup, N, rc.as<uint32_t>(), (const uint64_t*)nullptr,
-                               (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr);
-            FSM_LAUNCHED("k_rows_keep", s);
-        }
-        scan_exclusive(rc.as<uint32_t>(), off64.as<uint64_t>(), N, s);
-        FSM_HIP(hipMemcpyAsync(&E2, off64.as<uint64_t>() + N, 8, hipMemcpyDeviceToHost, s));
-        FSM_HIP(hipStreamSynchronize(s));
-        k_off.alloc((N + 1) * 4);
-        k_item.alloc(std::max<uint64_t>(E2, 1) * 4);
-        k_first.alloc(std::max<uint64_t>(E2, 1) * 4);
-        k_last.alloc(std::max<uint64_t>(E2, 1) * 4);
-        k_sup.alloc(std::max<uint64_t>(E2, 1) * 4);
-        hipLaunchKernelGGL(k_off32, dim3(unsigned(std::min<uint64_t>((N + 256) / 256, 4096))), dim3(256), 0, s,
-                           off64.as<uint64_t>(), N, k_off.as<uint32_t>());
-        FSM_LAUNCHED("k_off32", s);
-        if (N) {
-            hipLaunchKernelGGL(k_rows_keep, dim3(rows_grid), dim3(kBlock), 0, s, d->row_off.as<uint32_t>(),
-                               d->item.as<uint32_t>(), d->first.as<uint32_t>(), d->last.as<uint32_t>(),
-                               d_sup.as<uint32_t>(), rp.minsup, N, (uint32_t*)nullptr, off64.as<uint64_t>(),
-                               k_item.as<uint32_t>(), k_first.as<uint32_t>(), k_last.as<uint32_t>(),
-                               k_sup.as<uint32_t>());
-            FSM_LAUNCHED("k_rows_keep", s);
-        }
-        FSM_HIP(hipStreamSynchronize(s));
-    }
-    const double t1 = now_ms();
-    if (ctx->opts.verbose)
-        std::fprintf(stderr, "[fsm tsr] pair phase %.0f ms: minsup %u, candidates %zu, rules %zu, kept items %u, "
-                     "row entries %llu, %s path (ranks %d, keys exchanged %llu)\n",
-                     t1 - t0, rp.minsup, rp.cand.size(), rp.krules.size(), K, (unsigned long long)E2,
-                     use_bm ? "bitmap" : "list", R, (unsigned long long)rp_pair_exchanged);
-
-    // ---------------- expansions
-    // Batched speculation, committed in the exact sequential order: the next
-    // kExpBatch candidates (in heap order) are expanded together on the GPU;
-    // they are committed one by one while each is still the heap maximum; when
-    // a newly registered rule outranks the next one, the rest go back to the
-    // heap with their results cached (results are minsup-independent supersets,
-    // re-filtered against the current minsup at commit), so no expansion is
-    // computed twice and the outcome equals the one-at-a-time replay.
-    // Rules per launch (FSM_TSR_BATCH overrides, for tuning).  Wide batches halve the launches
-    // (round trips) where supports are coarse: at c4 (pair-phase minsup in the hundreds) every
-    // speculated rule is committed, and 768 rules per launch take 12,973 launches down to 7,179
-    // (2.76 -> 2.39 s).  Where supports are a few units (the 5K prefix ends at minsup 2) a wide
-    // batch's lowest rules sit at the threshold, their speculated children mostly fall below the
-    // rising minsup (1.45M speculated, 0.22M committed) and the launches multiply (2.6K -> 15K):
-    // those mines keep kExpBatch.
-    const uint32_t B = [&] {
-        const char* v = std::getenv("FSM_TSR_BATCH");
-        if (v) return uint32_t(std::clamp<long>(std::strtol(v, nullptr, 10), 1, kMaxBatch));
-        return uint32_t(rp.minsup >= kWideMinsup ? kExpBatchWide : kExpBatch);
-    }();
-    const uint64_t SU = uint64_t(B) * std::max<uint32_t>(U, 1);
-    const size_t kSidesB = B * sizeof(Side), kOffB = (B + 1) * 8;
-    // records per slot: at most one per candidate item (bitmap path: the kept items)
-    const uint32_t ecap = use_bm ? std::max<uint32_t>(K, 1) : std::max<uint32_t>(U, 1);
-    // bitmap path geometry: LDS histogram passes of KP kids; dense partial rows of
-    // 2 * KP counters per expansion block, at most max_blocks blocks per launch
-    const uint32_t pass_kids = [] {  // FSM_TSR_PASS_KIDS lowers the pass width (test hook: several passes)
-        const char* v = std::getenv("FSM_TSR_PASS_KIDS");
-        return v ? std::clamp<uint32_t>(uint32_t(std::strtoul(v, nullptr, 10)), 1, kPassKids) : kPassKids;
-    }();
-    const uint32_t KP = use_bm ? std::min<uint32_t>(K, pass_kids) : 0u;
-    const uint32_t P = use_bm ? (K + KP - 1) / KP : 0u;
-    const uint64_t row_bytes = uint64_t(P) * 2 * KP * 4;
-    const uint64_t part_mb = [] {  // FSM_TSR_PART_MB: partial-row budget per launch (tuning)
-        const char* v = std::getenv("FSM_TSR_PART_MB");
-        return v ? std::clamp<uint64_t>(std::strtoull(v, nullptr, 10), 1, 4096) : uint64_t(32);
-    }();
-    const uint64_t part_budget = std::max<uint64_t>(part_mb << 20, uint64_t(B) * row_bytes);
-    const uint64_t max_blocks = use_bm ? part_budget / row_bytes : 0;
-    const size_t xlds = use_bm ? (size_t(2) * KP + (K + 15) / 16) * 4 : 0;
-    // Two sets of launch buffers, so the GPU runs one launch while the host commits
-    // the results of the previous one.  A set holds the rule descriptors (pinned
-    // stage + device copy, one H2D copy per launch), the per-slot control blocks,
-    // the histograms (list path: per-slot HBM arrays; bitmap path: per-block partial
-    // rows and the domain lists), the results (mapped pinned host memory, at most
-    // ecap records per slot) and its own events (completion, per-kernel timing).
-    const TsrGrid grid;
-    // Sharded TSR (nranks > 1, bitmap path): each launch's rule slots are split over the
-    // ranks and the slots' results all-gathered once per launch (finish); the replay
-    // stays replicated and deterministic.  FSM_TSR_SHARD=0 replicates the expansions.
-    // FSM_TSR_DOMAIN=bitmap keeps every domain on the whole-bitmap AND (tests, A/B)
-    const int dom_mode = [] {  // 0 auto (by the rarest item's list length), 1 every slot bitmap, 2 every slot list
-        const char* v = std::getenv("FSM_TSR_DOMAIN");
-        return !v ? 0 : (!std::strcmp(v, "bitmap") ? 1 : (!std::strcmp(v, "list") ? 2 : 0));
-    }();
-    const bool shard_exp = shard && use_bm && [] {
-        const char* v = std::getenv("FSM_TSR_SHARD");
-        return !(v && v[0] == '0');
-    }();
-    // Kept-row lists (bitmap path, unsharded): an expansion keeps the rows where its rule holds
-    // with a non-empty suffix (sid, firstX | lastY, max X / max Y positions) in a per-mine device
-    // arena; a child rule's domain is then its parent's list with only the added item probed
-    // (a child holds only where its parent does).  Rules whose parent list did not fit the arena
-    // probe the whole bitmap AND.  FSM_TSR_PLIST=0 turns the lists off.
-    // A launch is sharded only when its expected domain (sum of 2 sup + 1 over its rules) reaches
-    // FSM_TSR_SHARD_MIN (default 256K sids: about 60 us of kernels at c4, the break-even of a
-    // per-launch gather); smaller launches run replicated on every rank (no gather), so the many
-    // small speculation launches of a c4-sized mine cost no exchange
-    const uint64_t shard_min = [] {
-        const char* v = std::getenv("FSM_TSR_SHARD_MIN");
-        return v ? std::strtoull(v, nullptr, 10) : uint64_t(1) << 18;
-    }();
-    // (the lists are rank-local: a rank keeps the lists of the slots it expanded, a child of
-    // another rank's slot probes the bitmaps; the counts are the same either way)
-    const bool plist = use_bm && [] {
-        const char* v = std::getenv("FSM_TSR_PLIST");
-        return !(v && v[0] == '0');
-    }();
-    // The arena is a ring: a launch writes its rules' lists (each at most the rule's support)
-    // at the head, at most acap / (4 nsets) entries (else it keeps none); a child reads its
-    // parent's list only while it lies within acap / 2 of the head.  A launch may stay in
-    // flight (its set not yet finished by the replay) while later launches advance the head,
-    // so each set records the oldest ring position it reads or writes (ExpSet::amin), and a
-    // launch that would overwrite that position finishes the set first (launch()).
-    DevBuf arena;
-    uint64_t acap = 0;   // arena entries (16 B)
-    uint64_t ahead = 0;  // the ring's head (entries written, monotonic; a list's position mod acap)
-    if (plist) {
-        size_t fr = 0, tot = 0;
-        FSM_HIP(hipMemGetInfo(&fr, &tot));
-        // lists for about the whole mine: the rows where a rule holds summed over the expansions
-        // reach a few thousand per sequence (c4: 2.0 G entries)
-        acap = std::min<uint64_t>({fr / (4 * uint64_t(ctx->dev_share)), uint64_t(64) << 30,
-                                   std::max<uint64_t>(uint64_t(64) << 20, uint64_t(d->NW) * 32 * 4096 * sizeof(uint4))}) /
-               sizeof(uint4);
-        if (const char* v = std::getenv("FSM_TSR_ARENA_MB"))  // (fractions of a MiB: tests)
-            acap = uint64_t(std::strtod(v, nullptr) * double(1u << 20)) / sizeof(uint4);
-        if (acap) arena.alloc(acap * sizeof(uint4));
-    }
-    // a child reads its parent's list while it lies within this many entries of the head
-    // (16/16: while no later write has reached it yet): acap / 2 by default, which keeps every
-    // list a launch in flight reads clear of the later launches' writes;
-    // FSM_TSR_PLIST_WINDOW=<sixteenths of the ring> (tests: 16 makes the in-flight guard below
-    // fire, its waits counted in fsm_stats.tsr_ring_waits)
-    const uint64_t plist_window = [&] {
-        const char* v = std::getenv("FSM_TSR_PLIST_WINDOW");
-        return acap / 16 * uint64_t(v ? std::clamp(std::atoi(v), 1, 16) : 8);
-    }();
-    // |sids(X u {c})| memo (bitmap path; FSM_TSR_DLMEMO=0 turns it off): zeroed once per mine
-    DevBuf memo_buf;
-    DlMemo memo{nullptr, 0u};
-    if (use_bm && [] { const char* v = std::getenv("FSM_TSR_DLMEMO"); return !(v && v[0] == '0'); }()) {
-        // 2^24 entries (256 MiB); FSM_TSR_DLMEMO_LOG2 (tests: a tiny table fills, probes run out)
-        const char* lv = std::getenv("FSM_TSR_DLMEMO_LOG2");
-        const uint32_t ent = 1u << (lv ? std::clamp(std::atoi(lv), 4, 28) : 24);
-        memo_buf.alloc(size_t(ent) * sizeof(uint4));
-        FSM_HIP(hipMemsetAsync(memo_buf.p, 0, size_t(ent) * sizeof(uint4), s));
-        FSM_HIP(hipStreamSynchronize(s));  // (the launches run on the sets' own streams)
-        memo = DlMemo{memo_buf.as<uint4>(), ent - 1u};
-    }
-    struct ExpSet {
-        DevBuf TL, DL, TR, seen, list, ctl, d_stage, d_dlw, d_ndlw, part, dom;
-        std::unique_ptr<PinnedBuf> stage, pin;
-        Side* h_sides = nullptr;
-        uint64_t *h_drv = nullptr, *h_wave = nullptr;
-        Side* d_sides = nullptr;
-        uint64_t *d_drv = nullptr, *d_wave = nullptr;
-        ExpHdr *h_hdr = nullptr, *d_hdr = nullptr;
-        ExpRec *h_rec = nullptr, *d_rec = nullptr;
-        uint32_t *h_rcnt = nullptr, *d_rcnt = nullptr;  // bitmap path: records per reduce block
-        std::vector<Rule*> batch;
-        std::vector<char> drv_in_x;
-        std::vector<uint64_t> kmono;  // bitmap path: each slot's kept-row list (ring position; kNoList: none)
-        uint64_t amin = kNoList;      // the oldest ring position the launch reads or writes (kNoList: none)
-        bool sharded = false;         // this launch's slots split over the ranks (results gathered)
-        uint32_t la = 0, lz = 0;  // slot sharding: this rank's slots [la, lz) of the batch (else all)
-        hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // 0-4 timing, 5 done
-        // the set's own stream: the two sets' launches are independent, so the GPU runs
-        // one set's kernels while the other's are in flight
-        hipStream_t st = nullptr;
-        bool own_stream = false;
-        DevBuf alive;          // kid codes for alive_t (each set its own: k_alive never races a launch)
-        uint32_t alive_t = 0;  // minsup the set's kid codes were built for
-        bool timed = false, busy = false;
-        int depth = 0;        // speculation depth of the batch (0: heap batch)
-        int64_t seq = 0;      // launch number (the older busy set finishes first)
-        uint64_t blocks = 0;  // expansion blocks of the launch
-        ~ExpSet() {  // (unwinding: the launch may still be running on buffers about to be freed)
-            if (busy && ev[5]) (void)hipEventSynchronize(ev[5]);
-            for (hipEvent_t e : ev)
-                if (e) (void)hipEventDestroy(e);
-            if (own_stream && st) {
-                (void)hipStreamSynchronize(st);
-                (void)hipStreamDestroy(st);
-            }
-        }
-    };
-    const int nsets = [] {  // launch sets in flight (FSM_TSR_SETS, 2-4)
-        const char* v = std::getenv("FSM_TSR_SETS");
-        return v ? std::clamp(std::atoi(v), 2, 4) : kExpSets;
-    }();
-    std::unique_ptr<ExpSet[]> xs_own(new ExpSet[nsets]);
-    ExpSet* const xs = xs_own.get();
-    for (int xi = 0; xi < nsets; ++xi) {
-        ExpSet& x = xs[xi];
-        FSM_HIP(hipStreamCreateWithFlags(&x.st, hipStreamNonBlocking));
-        x.own_stream = true;
-        if (use_bm) x.alive.alloc(size_t((K + 15) / 16) * 4);
-        x.ctl.alloc(B * sizeof(ExpCtl));
-        FSM_HIP(hipMemsetAsync(x.ctl.p, 0, B * sizeof(ExpCtl), s));
-        if (use_bm) {
-            x.part.alloc(max_blocks * row_bytes);
-            x.d_dlw.alloc(uint64_t(B) * ecap * sizeof(uint4));
-        } else {
-            x.TL.alloc(SU * 4);
-            x.DL.alloc(SU * 4);
-            x.TR.alloc(SU * 4);
-            x.seen.alloc(SU * 4);
-            x.list.alloc(SU * 4);
-            FSM_HIP(hipMemsetAsync(x.TL.p, 0, SU * 4, s));
-            FSM_HIP(hipMemsetAsync(x.DL.p, 0, SU * 4, s));
-            FSM_HIP(hipMemsetAsync(x.TR.p, 0, SU * 4, s));
-            FSM_HIP(hipMemsetAsync(x.seen.p, 0, SU * 4, s));
-        }
-        x.stage = std::make_unique<PinnedBuf>(kSidesB + 2 * kOffB);
-        x.d_stage.alloc(kSidesB + 2 * kOffB);
-        // [drv offsets | wave offsets | sides]: a launch copies the offsets and its nb sides
-        x.h_drv = static_cast<uint64_t*>(x.stage->host);
-        x.h_wave = x.h_drv + (B + 1);
-        x.h_sides = reinterpret_cast<Side*>(static_cast<char*>(x.stage->host) + 2 * kOffB);
-        x.d_drv = x.d_stage.as<uint64_t>();
-        x.d_wave = x.d_drv + (B + 1);
-        x.d_sides = reinterpret_cast<Side*>(x.d_stage.as<char>() + 2 * kOffB);
-        x.d_ndlw.alloc(16);
-        // [headers | records, ecap per slot | bitmap path: reduce region counts, B x P x collect]
-        const size_t nrc = use_bm ? size_t(B) * P * grid.collect : 0;
-        x.pin = std::make_unique<PinnedBuf>(B * sizeof(ExpHdr) + B * size_t(ecap) * sizeof(ExpRec) + nrc * 4);
-        x.h_hdr = static_cast<ExpHdr*>(x.pin->host);
-        x.h_rec = reinterpret_cast<ExpRec*>(x.h_hdr + B);
-        x.h_rcnt = reinterpret_cast<uint32_t*>(x.h_rec + size_t(B) * ecap);
-        x.d_hdr = static_cast<ExpHdr*>(x.pin->dev);
-        x.d_rec = reinterpret_cast<ExpRec*>(x.d_hdr + B);
-        x.d_rcnt = reinterpret_cast<uint32_t*>(x.d_rec + size_t(B) * ecap);
-        for (int q = 0; q < 5; ++q) FSM_HIP(hipEventCreate(&x.ev[q]));
-        FSM_HIP(hipEventCreateWithFlags(&x.ev[5], hipEventDisableTiming));
-    }
-    FSM_HIP(hipStreamSynchronize(s));  // the DB, kid tables and set buffers are ready for the set streams
-    // Expansion results of rules not yet committed: slots of a pool (Rule::res; a deque,
-    // so slots never move; released slots keep their vectors' capacity for the next
-    // rule).  Rules in flight carry their launch set in Rule::inset.
-    struct ExpResult {
-        std::vector<ExpRec> recs;
-        std::vector<Rule*> preL, preR;  // children created (and expanded) ahead of the commit, by record
-        Rule* owner = nullptr;
-    };
-    std::deque<ExpResult> res_pool;
-    std::vector<int32_t> res_free;
-    size_t res_live = 0;
-    auto res_get = [&](Rule* r) -> ExpResult& {
-        if (r->res < 0) {
-            if (res_free.empty()) {
-                res_free.push_back(int32_t(res_pool.size()));
-                res_pool.emplace_back();
-            }
-            r->res = res_free.back();
-            res_free.pop_back();
-            res_pool[size_t(r->res)].owner = r;
-            ++res_live;
-        }
-        return res_pool[size_t(r->res)];
-    };
-    auto res_release = [&](Rule* r) {
-        ExpResult& e = res_pool[size_t(r->res)];
-        e.recs.clear();
-        e.preL.clear();
-        e.preR.clear();
-        e.owner = nullptr;
-        res_free.push_back(r->res);
-        r->res = -1;
-        --res_live;
-    };
-    std::vector<std::pair<std::vector<Rule*>, int>> spec_todo;  // finished launches whose children to speculate
-    // speculated rules committed, and dropped at their parent's commit (verbose)
-    int64_t spec_hit = 0, spec_waste = 0;
-    int64_t expansions = 0, launches = 0, spec_pushback = 0, gpu_rules = 0;
-    double wait_ms = 0;  // host time blocked on the GPU in the expansion loop
-    double last_log_ms = now_ms();  // verbose progress line every 20 s
-    double prep_ms = 0, post_ms = 0, commit_ms = 0, pop_ms = 0;  // host time split (verbose summary)
-    double fill_ms = 0;  // launch prep: descriptor fill (the rest is the HIP calls)
-
-    const uint64_t exp_spb = [] {  // bitmap path: target domain sids per expansion block (FSM_TSR_SPB, tuning)
-        const char* v = std::getenv("FSM_TSR_SPB");
-        return v ? std::clamp<uint64_t>(std::strtoull(v, nullptr, 10), 1, 1u << 20) : uint64_t(kExpSpb);
-    }();
-    const uint64_t pl_spb = [] {  // parent-list rows per row block (one probe each: cheaper than a domain sid)
-        const char* v = std::getenv("FSM_TSR_PLSPB");
-        return v ? std::clamp<uint64_t>(std::strtoull(v, nullptr, 10), 1, 1u << 20) : uint64_t(kExpSpb);
-    }();
-    // per-kernel device time: every 16th launch records one set of events and reads
-    // them back when it finishes (ctx->kstats rows); FSM_TSR_TIME_EVERY=n times every n-th
-    // (1: every launch, the bench's roofline mine)
-    const int64_t time_every = [] {
-        const char* v = std::getenv("FSM_TSR_TIME_EVERY");
-        return v ? std::clamp<int64_t>(std::strtoll(v, nullptr, 10), 1, 1 << 20) : int64_t(16);
-    }();
-    struct Seg {
-        double ms = 0;  // over the timed launches
-        int64_t n = 0, timed = 0, bytes = 0, survey = 0;  // survey: SURVEY §8(d) TSR units
-    } seg[4];  // bitmap path: domain, rows, reduce, k_dl; list path: expansion, -, collect, k_publish
-    const char* seg_name[4] = {use_bm ? "k_exp_domain" : "k_expand", use_bm ? "k_exp_rows" : "",
-                               use_bm ? "k_expand_reduce" : "k_expand_collect", use_bm ? "k_dl" : "k_publish"};
-    int64_t exp_domain = 0, exp_entries = 0, exp_bitmap_bytes = 0, exp_part_bytes = 0;
-    int64_t exp_hold = 0, exp_walk = 0;  // domain rows where the rule holds, row entries walked (verbose)
-    int64_t exp_plist = 0;               // expansions whose domain came from the parent's kept rows (verbose)
-    int64_t ring_waits = 0;              // launches in flight finished early to free their ring positions
-    int64_t seq_next = 0;
-    // Take in the results of set x (waits for its launch): records sorted into the
-    // cache, and its batch queued for child speculation.
-    auto finish = [&](ExpSet& x) {
-        const double tw0 = now_ms();
-        FSM_HIP(hipEventSynchronize(x.ev[5]));
-        const double tw1 = now_ms();
-        wait_ms += tw1 - tw0;
-        x.busy = false;
-        for (int q = 0; q < 4; ++q) {
-            float ms = 0;
-            if (x.timed && hipEventElapsedTime(&ms, x.ev[q], x.ev[q + 1]) == hipSuccess) {
-                seg[q].ms += ms;
-                seg[q].timed += 1;
-            }
-            seg[q].n += 1;
-        }
-        const uint32_t nb = x.lz - x.la;  // the slots expanded here (slot sharding: this rank's share)
-        if (use_bm && nb) {
-            exp_part_bytes += int64_t(x.blocks * row_bytes);
-            seg[1].bytes += int64_t(x.blocks * row_bytes);  // the partial rows the row kernel writes
-        }
-        uint64_t nout_all = 0;
-        ctx->stats.rank_units += int64_t(nb);
-        for (uint32_t k = 0; k < nb; ++k) {
-            Rule* r = x.batch[x.la + k];
-            const ExpHdr h = x.h_hdr[k];
-            nout_all += h.nout;
-            if (use_bm) {
-                // own bytes: domain = the |X|+|Y| bitmap operands + 4 B written per domain sid;
-                // rows = per domain sid its id and row bounds (12 B) and |X u Y| probes (rank
-                // directory 4 B + bitmap words 16 B + vertical entry 8 B), or per parent row 16 B
-                // and one probe (plist), + 8 B per entry walked + 16 B per kept row written
-                const bool pm = x.h_sides[k].lmode == 2;
-                const uint64_t bmb = pm ? 0ull : uint64_t(r->nx + r->ny) * d->NW * 4;
-                const uint64_t ndom = pm ? r->pn : h.nsid;
-                exp_domain += ndom;
-                exp_entries += h.nent;
-                exp_hold += h.nhold;
-                exp_walk += h.nwalk;
-                exp_plist += pm ? 1 : 0;
-                exp_bitmap_bytes += int64_t(bmb);
-                seg[0].bytes += int64_t(bmb + 4ull * (pm ? 0ull : h.nsid));
-                seg[1].bytes += int64_t(8ull * h.nwalk + (pm ? 44ull : 12ull + 28ull * (r->nx + r->ny)) * ndom +
-                                        (x.kmono[k] != kNoList ? 16ull * h.ln : 0ull));
-                // SURVEY: N/8 B per sid-bitmap operand; 4 B token + 4 B first/last per position of
-                // every sequence where the rule holds (the reference scans each of them whole)
-                seg[0].survey += int64_t(bmb);
-                seg[1].survey += int64_t(8ull * h.nent);
-                // the rule's kept rows (more than its support: the list was cut, none kept)
-                r->loff = x.kmono[k] != kNoList && h.ln <= x.h_sides[k].kb ? x.kmono[k] : kNoList;
-                r->ln = h.ln;
-            }
-            if (h.nout > ecap) throw Error(FSM_ELIMIT, "TSR: expansion candidate buffer overflow");
-            if (!use_bm && x.drv_in_x[k] && h.nx != r->nX)
-                throw Error(FSM_EDEVICE, "TSR: |sids(X)| mismatch in expansion (" + std::to_string(h.nx) + " vs " +
-                                             std::to_string(r->nX) + ")");
-            r->inset = -1;
-            if (r->dropped) continue;  // a speculated child its parent's commit did not register
-            ExpResult& res = res_get(r);
-            const ExpRec* rec = x.h_rec + size_t(k) * ecap;
-            if (use_bm) {  // the reduce blocks' kid ranges, in kid (= item) order
-                res.recs.clear();
-                res.recs.reserve(h.nout);
-                const uint32_t* rc = x.h_rcnt + size_t(k) * P * grid.collect;
-                const uint32_t q = (KP + grid.collect - 1) / grid.collect;
-                for (uint32_t p = 0; p < P; ++p)
-                    for (uint32_t g = 0; g < grid.collect; ++g) {
-                        const ExpRec* r0 = rec + size_t(p) * KP + size_t(g) * q;
-                        res.recs.insert(res.recs.end(), r0, r0 + rc[p * grid.collect + g]);
-                    }
-            } else {
-                res.recs.assign(rec, rec + h.nout);
-                std::sort(res.recs.begin(), res.recs.end(), [](const ExpRec& a, const ExpRec& c) { return a.c < c.c; });
-            }
-        }
-        if (x.sharded) {
-            // every rank's slots: (nsid, nent, nrec, records) per slot of its share, gathered
-            // once per launch (the failure agreement rides along); the replay then goes on
-            // alike on every rank
-            std::vector<uint8_t> mine;
-            auto put = [&](const void* p, size_t n) {
-                const uint8_t* b = static_cast<const uint8_t*>(p);
-                mine.insert(mine.end(), b, b + n);
-            };
-            for (uint32_t k = 0; k < nb; ++k) {
-                Rule* r = x.batch[x.la + k];
-                const ExpHdr h = x.h_hdr[k];
-                const uint32_t nrec = r->dropped || r->res < 0 ? 0u : uint32_t(res_pool[size_t(r->res)].recs.size());
-                const uint32_t hd[3] = {h.nsid, h.nent, nrec};
-                put(hd, sizeof(hd));
-                if (nrec) put(res_pool[size_t(r->res)].recs.data(), nrec * sizeof(ExpRec));
-            }
-            std::vector<size_t> sizes;
-            const std::vector<uint8_t> all = comm->gather_blobs(mine, sizes, s, &agr);
-            // the ranks' blobs hold their contiguous slot ranges, in rank and slot order
-            size_t at = 0;
-            uint32_t k = 0;
-            for (int q = 0; q < R; ++q) {
-                const size_t end = at + sizes[size_t(q)];
-                for (; k < x.batch.size() && at < end; ++k) {
-                    uint32_t hd[3];
-                    std::memcpy(hd, all.data() + at, sizeof(hd));
-                    at += sizeof(hd);
-                    Rule* r = x.batch[k];
-                    if (q != comm->rank()) {
-                        exp_domain += hd[0];
-                        exp_entries += hd[1];
-                        r->inset = -1;
-                        if (!r->dropped) {
-                            ExpResult& res = res_get(r);
-                            res.recs.resize(hd[2]);
-                            if (hd[2]) std::memcpy(res.recs.data(), all.data() + at, hd[2] * sizeof(ExpRec));
-                        }
-                    }
-                    at += size_t(hd[2]) * sizeof(ExpRec);
-                }
-            }
-            if (at != all.size()) throw Error(FSM_EDEVICE, "TSR: sharded expansion results out of step");
-        }
-        seg[2].bytes += int64_t(nout_all * sizeof(ExpRec));
-        x.timed = false;
-        spec_todo.emplace_back(std::move(x.batch), x.depth);
-        x.batch.clear();
-        post_ms += now_ms() - tw1;
-    };
-    // expand `batch` on a free set (finishing the older busy one first when both are
-    // busy): enqueue the launch and return; finish() takes the results in
-    auto launch = [&](const std::vector<Rule*>& batch, int depth) {
-        ExpSet* xp = nullptr;
-        for (int xi = 0; xi < nsets && !xp; ++xi)
-            if (!xs[xi].busy) xp = &xs[xi];
-        if (!xp) {  // every set busy: the oldest launch finishes first
-            xp = &xs[0];
-            for (int xi = 1; xi < nsets; ++xi)
-                if (xs[xi].seq < xp->seq) xp = &xs[xi];
-            finish(*xp);
-        }
-        ExpSet& x = *xp;
-        const double tl0 = now_ms();
-        x.batch = batch;
-        x.depth = depth;
-        x.seq = seq_next++;
-        for (Rule* r : batch) {
-            r->inset = int8_t(xp - xs);
-            // every rule of the batch (not only this rank's slots): its children's X ids derive from it
-            if (r->xid == kNone) r->xid = rp.xin.get(r->pxid, rp.st.X(r)[r->nx - 1]);
-        }
-        // slot sharding: this rank expands only its contiguous share of the batch, split so
-        // that the shares' expected domains (about twice each rule's support) are equal
-        x.la = 0;
-        x.lz = uint32_t(batch.size());
-        x.sharded = false;
-        uint64_t tot = 0;
-        if (shard_exp)
-            for (Rule* r : batch) tot += 2ull * r->sup + 1;
-        if (shard_exp && tot >= shard_min) {
-            x.sharded = true;
-            const uint64_t lo = tot * uint64_t(comm->rank()) / uint64_t(R), hi = tot * uint64_t(comm->rank() + 1) / uint64_t(R);
-            uint64_t acc = 0;
-            x.la = x.lz = uint32_t(batch.size());
-            for (uint32_t k = 0; k < batch.size(); ++k) {  // slot k belongs to the rank whose range holds its start
-                if (acc >= lo && x.la == batch.size()) x.la = k;
-                if (acc >= hi) { x.lz = k; break; }
-                acc += 2ull * batch[k]->sup + 1;
-            }
-            if (x.lz < x.la) x.lz = x.la;
-        }
-        const uint32_t nb = x.lz - x.la;  // slots launched here
-        const Rule* const* bp = batch.data() + x.la;
-        gpu_rules += nb;
-        // descriptors written in place into the set's pinned stage (only the used items:
-        // the kernels read X[0, nx) and Y[0, ny))
-        uint64_t* drv_off = x.h_drv;
-        uint64_t* wave_off = x.h_wave;
-        drv_off[0] = wave_off[0] = 0;
-        x.drv_in_x.assign(nb, 1);
-        for (uint32_t k = 0; k < nb; ++k) {
-            const Rule* r = bp[k];
-            const uint32_t *rx = rp.st.X(r), *ry = rp.st.Y(r);
-            Side& sd = x.h_sides[k];
-            sd.nx = r->nx;
-            sd.ny = r->ny;
-            sd.doL = r->expandLR;
-            sd.doR = 1;
-            sd.maxX = rx[r->nx - 1];
-            sd.maxY = ry[r->ny - 1];
-            std::copy(rx, rx + r->nx, sd.X);
-            std::copy(ry, ry + r->ny, sd.Y);
-            sd.pc = sd.pleft = sd.pn = sd.kb = 0;
-            sd.pl = 0;
-            sd.ko = kNoList;
-            sd.xid = r->xid;  // (the memo key of its left extensions)
-            sd.klo = use_bm ? std::min(h_kid_of[rx[r->nx - 1]], h_kid_of[ry[r->ny - 1]]) + 1u : 0u;
-            if (use_bm && plist && r->ploff != kNoList && r->ploff + plist_window >= ahead) {
-                // the parent's kept rows (still in the ring) are the domain: only the added item is
-                // probed there
-                wave_off[k + 1] = wave_off[k] + std::clamp<uint64_t>((uint64_t(r->pn) + pl_spb - 1) / pl_spb, 1,
-                                                                     grid.expand);
-                drv_off[k + 1] = drv_off[k];
-                sd.drv = 0;
-                sd.lmode = 2;
-                sd.pc = r->pc;
-                sd.pleft = r->pleft ? 1u : 0u;
-                sd.pn = r->pn;
-                sd.pl = r->ploff % acap;
-            } else if (use_bm) {
-                // bitmap path: row blocks sized by the expected domain (about twice the rule's
-                // support: sids holding X u Y in either order), exp_spb sids per block; the
-                // domain list holds at most the support of the rarest item of X u Y
-                wave_off[k + 1] = wave_off[k] + std::clamp<uint64_t>((2ull * r->sup + exp_spb - 1) / exp_spb, 1,
-                                                                     grid.expand);
-                uint32_t cap = kNone, drv = rx[0];
-                for (uint32_t q = 0; q < r->nx; ++q) if (sup[rx[q]] < cap) { cap = sup[rx[q]]; drv = rx[q]; }
-                for (uint32_t q = 0; q < r->ny; ++q) if (sup[ry[q]] < cap) { cap = sup[ry[q]]; drv = ry[q]; }
-                drv_off[k + 1] = drv_off[k] + cap;
-                sd.drv = drv;
-                sd.lmode = dom_mode == 2 || (dom_mode == 0 && uint64_t(cap) * 4 < d->NW) ? 1u : 0u;
-            } else {
-                // list path: one wave per sid of the driver list: the rarest item of X
-                // (expandL needs all of sids(X)), else of X u Y
-                uint32_t drv = rx[0];
-                for (uint32_t q = 0; q < r->nx; ++q) if (sup[rx[q]] < sup[drv]) drv = rx[q];
-                if (!r->expandLR)
-                    for (uint32_t q = 0; q < r->ny; ++q) if (sup[ry[q]] < sup[drv]) { drv = ry[q]; x.drv_in_x[k] = 0; }
-                drv_off[k] = voff[drv];
-                wave_off[k + 1] = wave_off[k] + (voff[drv + 1] - voff[drv]);
-            }
-        }
-        x.kmono.assign(nb, kNoList);
-        x.amin = kNoList;
-        for (uint32_t k = 0; k < nb; ++k)
-            if (x.h_sides[k].lmode == 2) x.amin = std::min(x.amin, bp[k]->ploff);
-        if (plist && acap) {  // the slots' kept-row lists at the ring's head, each at most the rule's support
-            uint64_t need = 0;
-            for (uint32_t k = 0; k < nb; ++k) need += bp[k]->sup;
-            // (the head skips to the ring's start when a list would wrap)
-            const uint64_t at = ahead % acap + need > acap ? ahead + acap - ahead % acap : ahead;
-            // a launch never overwrites the parent lists its own slots read (x.amin): it keeps
-            // no lists then (only a parent window wider than the default can come this close)
-            const bool own_ok = x.amin == kNoList || x.amin + acap >= at + need;
-            if (need && need <= acap / (4 * uint64_t(nsets)) && own_ok) {
-                ahead = at;
-                // positions below ahead + need - acap are overwritten now: a set still in flight
-                // that reads or writes one of them is finished first (its results are taken in)
-                for (int xi = 0; xi < nsets; ++xi) {
-                    ExpSet& o = xs[xi];
-                    if (&o != &x && o.busy && o.amin != kNoList && o.amin + acap < ahead + need) {
-                        // its kernels completed is all the ring needs (its results are taken in at
-                        // their turn: a finish here would be a rank-local collective when sharded)
-                        FSM_HIP(hipEventSynchronize(o.ev[5]));
-                        o.amin = kNoList;
-                        ++ring_waits;
-                    }
-                }
-                x.amin = std::min(x.amin, ahead);
-                for (uint32_t k = 0; k < nb; ++k) {
-                    x.h_sides[k].ko = ahead % acap;
-                    x.h_sides[k].kb = bp[k]->sup;
-                    x.kmono[k] = ahead;
-                    ahead += bp[k]->sup;
-                }
-            }
-        }
-        if (use_bm && wave_off[nb] > max_blocks) {
-            // partial rows over budget: the budget is shared in proportion to the slots'
-            // expected domains (the launch lasts as long as its largest slot's blocks), at
-            // least one block each
-            const uint64_t tot = wave_off[nb];
-            uint64_t prev = 0;  // the original prefix at k
-            for (uint32_t k = 0; k < nb; ++k) {
-                const uint64_t n0 = wave_off[k + 1] - prev;
-                prev = wave_off[k + 1];
-                wave_off[k + 1] = wave_off[k] + std::max<uint64_t>(1, n0 * (max_blocks - nb) / tot);
-            }
-        }
-        x.blocks = wave_off[nb];
-        if (use_bm && x.dom.bytes < drv_off[nb] * 4)
-            x.dom.alloc(std::max<uint64_t>(drv_off[nb] * 4 * 5 / 4, uint64_t(1) << 20));
-        fill_ms += now_ms() - tl0;
-        hipStream_t s = x.st;  // (shadows the context stream for this launch)
-        // the descriptors by a copy kernel on the set's stream (reading the mapped staging over PCIe:
-        // an SDMA copy would cost the launch's first kernel a cross-engine wait)
-        static_assert(sizeof(Side) % 4 == 0, "Side: whole words");
-        copy_from_mapped(x.d_stage.p, x.stage->dev, 2 * kOffB + size_t(nb) * sizeof(Side), s);
-        x.timed = nb && launches % time_every == 0;  // every 16th launch is timed (events cost host time)
-        const ExpGeo geo{K, KP, uint32_t(wave_off[nb]), rp.minsup};
-        if (nb) {  // (a rank may get no slot of a small sharded batch)
-            if (use_bm && x.alive_t != rp.minsup) {  // minsup rose: the kids below it stop counting
-                hipLaunchKernelGGL(k_alive, dim3(unsigned(((K + 15) / 16 + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
-                                   d_ksup.as<uint32_t>(), K, rp.minsup, x.alive.as<uint32_t>());
-                FSM_LAUNCHED("k_alive", s);
-                x.alive_t = rp.minsup;
-            }
-            if (x.timed) FSM_HIP(hipEventRecord(x.ev[0], s));
-            bool any_dom = false;  // (every slot on its parent's kept rows: no domain kernel)
-            for (uint32_t k = 0; k < nb && !any_dom; ++k) any_dom = x.h_sides[k].lmode != 2;
-            if (use_bm) {
-                if (any_dom) {
-                    hipLaunchKernelGGL(k_exp_domain, dim3((d->NW + kDomWords - 1) / kDomWords, nb), dim3(kDomThreads),
-                                       0, s, x.d_sides, d->bm.as<uint32_t>(), d->NW, x.d_drv, x.dom.as<uint32_t>(),
-                                       x.ctl.as<ExpCtl>(), d->vert_off.as<uint64_t>(), d->vert_sid.as<uint32_t>());
-                    FSM_LAUNCHED("k_exp_domain", s);
-                }
-                if (x.timed) FSM_HIP(hipEventRecord(x.ev[1], s));
-                hipLaunchKernelGGL(k_exp_rows, dim3(unsigned(wave_off[nb]), P), dim3(kXBlock), xlds, s, x.d_sides,
-                                   x.d_wave, nb, x.d_drv, x.dom.as<uint32_t>(), k_off.as<uint32_t>(), k_ent.as<uint2>(),
-                                   d_kidof.as<uint32_t>(), x.alive.as<uint32_t>(), geo, x.part.as<uint32_t>(),
-                                   x.ctl.as<ExpCtl>(), x.d_ndlw.as<uint32_t>(),
-                                   DomProbe{d->bm.as<uint32_t>(), d->NW, d->NW / 4, d_rdir.as<uint32_t>(),
-                                            d_kvoff.as<uint32_t>(), d_vfl.as<uint2>()},
-                                   arena.as<uint4>());
-                FSM_LAUNCHED("k_exp_rows", s);
-                if (x.timed) FSM_HIP(hipEventRecord(x.ev[2], s));
-                hipLaunchKernelGGL(k_expand_reduce, dim3(grid.collect, nb, P), dim3(kBlock), 0, s, x.part.as<uint32_t>(),
-                                   x.d_wave, geo, d_kept.as<uint32_t>(), x.ctl.as<ExpCtl>(), x.d_rec, ecap,
-                                   x.d_dlw.as<uint4>(), x.d_ndlw.as<uint32_t>(), x.d_rcnt, x.d_sides, memo);
-                FSM_LAUNCHED("k_expand_reduce", s);
-                if (x.timed) FSM_HIP(hipEventRecord(x.ev[3], s));
-                hipLaunchKernelGGL(k_dl, dim3(grid.dl), dim3(kBlock), 0, s, x.d_sides, d->bm.as<uint32_t>(),
-                                   d->NW, d->vert_off.as<uint64_t>(), d->vert_sid.as<uint32_t>(), x.d_dlw.as<uint4>(),
-                                   x.d_ndlw.as<uint32_t>(), x.d_rec, ecap, x.ctl.as<ExpCtl>(), x.d_hdr, nb, memo);
-                FSM_LAUNCHED("k_dl", s);
-            } else {
-                const uint64_t waves = wave_off[nb];
-                if (waves) {
-                    hipLaunchKernelGGL(k_expand, dim3(unsigned((waves * 64 + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
-                                       x.d_sides, x.d_drv, x.d_wave, nb,
-                                       d->vert_sid.as<uint32_t>(), k_off.as<uint32_t>(), k_item.as<uint32_t>(),
-                                       k_first.as<uint32_t>(), k_last.as<uint32_t>(), U, x.TL.as<uint32_t>(),
-                                       x.DL.as<uint32_t>(), x.TR.as<uint32_t>(), x.seen.as<uint32_t>(),
-                                       x.list.as<uint32_t>(), x.ctl.as<ExpCtl>(), d_sup.as<uint32_t>(), rp.minsup);
-                    FSM_LAUNCHED("k_expand", s);
-                }
-                if (x.timed) FSM_HIP(hipEventRecord(x.ev[1], s));
-                if (x.timed) FSM_HIP(hipEventRecord(x.ev[2], s));
-                hipLaunchKernelGGL(k_expand_collect, dim3(grid.collect, nb), dim3(kBlock), 0, s, x.TL.as<uint32_t>(),
-                                   x.DL.as<uint32_t>(), x.TR.as<uint32_t>(), x.seen.as<uint32_t>(), x.list.as<uint32_t>(),
-                                   x.ctl.as<ExpCtl>(), U, rp.minsup, x.d_rec, ecap);
-                FSM_LAUNCHED("k_expand_collect", s);
-                if (x.timed) FSM_HIP(hipEventRecord(x.ev[3], s));
-                hipLaunchKernelGGL(k_publish, dim3(1), dim3(kBlock), 0, s, x.ctl.as<ExpCtl>(), x.d_hdr, nb);
-                FSM_LAUNCHED("k_publish", s);
-            }
-        }
-        if (x.timed) FSM_HIP(hipEventRecord(x.ev[4], s));
-        FSM_HIP(hipEventRecord(x.ev[5], s));
-        x.busy = true;
-        ++launches;
-        prep_ms += now_ms() - tl0;
-    };
-    // Speculated rules wait in `pending` (ordered like the heap, results
-    // cached or in flight) instead of going back to the heap: the next rule to
-    // commit is always the larger of the heap top and the pending front, which
-    // is exactly the one-at-a-time order; new rules only ever enter the heap.
-    // The rules of one batch pop leave the heap in its order, so `pending` is a
-    // merge of sorted runs (one per pop loop): a small heap of runs keyed by their
-    // fronts, no per-rule tree node.
-    struct PendingRuns {
-        const RuleStore* st;
-        struct Run {
-            std::vector<Rule*> v;  // largest first
-            size_t h = 0;          // front
-        };
-        std::vector<Run> runs;
-        std::vector<int> free_ids, heap;  // heap: live runs, the largest front on top
-        bool front_less(int a, int b) const {
-            return rule_cmp(*st, runs[size_t(a)].v[runs[size_t(a)].h], runs[size_t(b)].v[runs[size_t(b)].h]) < 0;
-        }
-        bool empty() const { return heap.empty(); }
-        Rule* front() const { return runs[size_t(heap[0])].v[runs[size_t(heap[0])].h]; }
-        void pop() {
-            auto cmp = [this](int a, int b) { return front_less(a, b); };
-            const int id = heap[0];
-            std::pop_heap(heap.begin(), heap.end(), cmp);
-            heap.pop_back();
-            Run& r = runs[size_t(id)];
-            if (++r.h < r.v.size()) {
-                heap.push_back(id);
-                std::push_heap(heap.begin(), heap.end(), cmp);
-            } else {
-                r.v.clear();
-                r.h = 0;
-                free_ids.push_back(id);
-            }
-        }
-        void add(std::vector<Rule*>& v) {  // v: in heap pop order; taken over (left empty)
-            if (v.empty()) return;
-            int id;
-            if (free_ids.empty()) {
-                id = int(runs.size());
-                runs.emplace_back();
-            } else {
-                id = free_ids.back();
-                free_ids.pop_back();
-            }
-            runs[size_t(id)].v.swap(v);
-            runs[size_t(id)].h = 0;
-            v.clear();
-            heap.push_back(id);
-            std::push_heap(heap.begin(), heap.end(), [this](int a, int b) { return front_less(a, b); });
-        }
-        uint32_t min_sup() const {  // support of the smallest pending rule (the runs' backs)
-            uint32_t m = 0xFFFFFFFFu;
-            for (int id : heap) m = std::min(m, runs[size_t(id)].v.back()->sup);
-            return m;
-        }
-    };
-    PendingRuns pending{&rp.st, {}, {}, {}};
-    std::vector<Rule*> popped;  // one pop loop's rules (a run of `pending`)
-    // a speculated child that its parent's commit did not register: drop its
-    // results (cached, or marked so that an in-flight launch's are discarded) and,
-    // recursively, those of its own speculated children
-    std::function<void(Rule*)> drop_spec = [&](Rule* x) {
-        x->dropped = true;
-        spec_waste += x->spec;
-        if (x->res < 0) return;
-        std::vector<Rule*> kids;
-        {
-            const ExpResult& e = res_pool[size_t(x->res)];
-            for (Rule* c : e.preL) if (c) kids.push_back(c);
-            for (Rule* c : e.preR) if (c) kids.push_back(c);
-        }
-        res_release(x);
-        for (Rule* c : kids) drop_spec(c);
-    };
-    auto commit = [&](Rule* r, ExpResult& res) {
-        const std::vector<ExpRec>& er = res.recs;
-        const bool pre = !res.preL.empty();
-        expansions += r->expandLR ? 2 : 1;
-        if (ctx->opts.verbose && now_ms() - last_log_ms > 20000.0 && (last_log_ms = now_ms()) > 0)
-            std::fprintf(stderr, "[fsm tsr] %lld expansions, minsup %u, candidates %zu, rules %zu, %.0f ms\n",
-                         (long long)expansions, rp.minsup, rp.cand.size(), rp.krules.size(), now_ms() - t0);
-        if (r->expandLR) {  // expandL: X u {c} => Y
-            for (size_t i = 0; i < er.size(); ++i) {
-                const ExpRec& e = er[i];
-                Rule* sp = pre ? res.preL[i] : nullptr;
-                if (e.tl == 0 || e.tl < rp.minsup) {
-                    if (sp) drop_spec(sp);
-                    continue;
-                }
-                Rule* nr = sp ? sp : rp.derive(r, e.c, kNone, e.tl, e.dl);
-                if (nr->conf >= minconf) rp.save(nr);
-                rp.reg(nr, true);
-            }
-        }
-        for (size_t i = 0; i < er.size(); ++i) {  // expandR: X => Y u {c}
-            const ExpRec& e = er[i];
-            Rule* sp = pre ? res.preR[i] : nullptr;
-            if (e.tr == 0 || e.tr < rp.minsup) {
-                if (sp) drop_spec(sp);
-                continue;
-            }
-            Rule* nr = sp ? sp : rp.derive(r, kNone, e.c, e.tr, r->nX);
-            if (nr->conf >= minconf) rp.save(nr);
-            rp.reg(nr, false);
-        }
-    };
-
-    // Child speculation: when a launch finishes, the children of its rules that
-    // rank at or above the lowest pending rule (sup >= T) are the ones whose
-    // registration would force the next launch (a fresh rule outranking the
-    // pending front).  They are created now, exactly as their parent's commit
-    // would create them, and expanded in a follow-up launch (a few levels deep)
-    // while the host commits; the commit then registers the pre-built rule
-    // (results cached or in flight) instead of deriving it again.
-    int64_t spec_made = 0, spec_launches = 0;
-    int spec_depth = kSpecDepth, spec_max = kSpecMax * int(B);  // FSM_TSR_SPEC="depth,max" (tuning; "0" disables)
-    double spec_frac = 1.0;  // FSM_TSR_SPEC_FRAC: speculate children with sup >= frac * T (tuning)
-    if (const char* v = std::getenv("FSM_TSR_SPEC_FRAC")) {
-        const double f = std::atof(v);
-        if (f > 0.0 && f <= 1.0) spec_frac = f;
-    }
-    if (const char* v = std::getenv("FSM_TSR_SPEC")) {
-        int a = 0, b2 = 0;
-        if (std::sscanf(v, "%d,%d", &a, &b2) == 2 && a >= 0 && a <= 64 && b2 > 0 && b2 <= 4096) {
-            spec_depth = a;
-            spec_max = b2;
-        }
-    }
-    const bool spec_on = [] { const char* v = std::getenv("FSM_TSR_SPEC"); return !(v && v[0] == '0'); }();
-    // the next level of one finished launch's batch
-    auto speculate = [&](const std::vector<Rule*>& level, int depth) {
-        if (!spec_on || depth >= spec_depth || level.empty()) return;
-        uint32_t T = 0xFFFFFFFFu;
-        for (Rule* x : level) T = std::min(T, x->sup);
-        if (!pending.empty()) T = std::min(T, pending.min_sup());
-        T = std::max(uint32_t(double(T) * spec_frac), rp.minsup);
-        std::vector<Rule*> next;
-        for (Rule* x : level) {
-            if (x->res < 0) continue;  // committed already, or dropped
-            ExpResult& res = res_pool[size_t(x->res)];
-            const size_t n = res.recs.size();
-            res.preL.assign(n, nullptr);
-            res.preR.assign(n, nullptr);
-            for (size_t i = 0; i < n && next.size() < size_t(spec_max); ++i) {
-                const ExpRec& e = res.recs[i];
-                if (x->expandLR && e.tl >= T) {
-                    Rule* c = rp.derive(x, e.c, kNone, e.tl, e.dl);
-                    c->expandLR = true;
-                    c->spec = true;
-                    res.preL[i] = c;
-                    next.push_back(c);
-                }
-                if (e.tr >= T && next.size() < size_t(spec_max)) {
-                    Rule* c = rp.derive(x, kNone, e.c, e.tr, x->nX);
-                    c->expandLR = false;
-                    c->spec = true;
-                    res.preR[i] = c;
-                    next.push_back(c);
-                }
-            }
-        }
-        spec_made += int64_t(next.size());
-        for (size_t a = 0; a < next.size(); a += size_t(B)) {
-            const std::vector<Rule*> part(next.begin() + a, next.begin() + std::min(next.size(), a + size_t(B)));
-            launch(part, depth + 1);
-            ++spec_launches;
-        }
-    };
-
-    std::vector<Rule*> batch;
-    size_t sweep_at = size_t(1) << 16;
-    for (;;) {
-        // children of finished launches first (their launches overlap the commits below)
-        while (!spec_todo.empty()) {
-            std::vector<std::pair<std::vector<Rule*>, int>> todo;
-            todo.swap(spec_todo);
-            for (auto& [lvl, dp] : todo) speculate(lvl, dp);
-        }
-        const bool have_h = !rp.cand.empty(), have_p = !pending.empty();
-        if (!have_h && !have_p) break;
-        const bool from_p = have_p && (!have_h || rule_cmp(rp.st, pending.front(), rp.cand.top().r) > 0);
-        Rule* r = from_p ? pending.front() : rp.cand.top().r;
-        if (r->sup < rp.minsup) break;
-        if (r->res < 0 && r->inset >= 0) {  // expanding on the GPU: take its launch in, then decide again
-            finish(xs[r->inset]);
-            continue;
-        }
-        if (r->res >= 0) {  // results at hand: commit now
-            if (from_p) pending.pop();
-            else rp.cand.pop();
-            // (the host-time split is taken only when verbose: a clock read costs as much as a commit)
-            const double tc0 = ctx->opts.verbose ? now_ms() : 0.0;
-            commit(r, res_pool[size_t(r->res)]);
-            spec_hit += r->spec;
-            if (r->res >= 0) res_release(r);
-            if (ctx->opts.verbose) commit_ms += now_ms() - tc0;
-            if (res_live > sweep_at) {  // results of rules now below minsup can never be committed
-                for (ExpResult& e : res_pool)
-                    if (e.owner && e.owner->sup < rp.minsup) res_release(e.owner);
-                sweep_at = std::max<size_t>(2 * res_live, 1u << 16);
-            }
-            continue;
-        }
-        if (from_p) throw Error(FSM_EDEVICE, "TSR: a pending rule has neither results nor a launch");
-        // r (neither cached nor in flight) and the next heap rules are expanded together
-        const double tp0 = now_ms();
-        batch.clear();
-        popped.clear();
-        while (batch.size() < size_t(B) && !rp.cand.empty() && uint32_t(rp.cand.top().k1 >> 32) >= rp.minsup) {
-            Rule* x = rp.cand.top().r;
-            rp.cand.pop();
-            popped.push_back(x);
-            if (x->res < 0 && x->inset < 0) batch.push_back(x);  // else already expanded by speculation
-        }
-        pending.add(popped);
-        pop_ms += now_ms() - tp0;
-        launch(batch, 0);
-        spec_pushback += int64_t(batch.size()) - 1;
-    }
-    for (int xi = 0; xi < nsets; ++xi)  // speculation still in flight when the replay ended
-        if (xs[xi].busy) finish(xs[xi]);
-    ctx->stats.tsr_ring_waits = ring_waits;
-    if (ctx->opts.verbose)
-        std::fprintf(stderr,
-                     "[fsm tsr] expansions %lld in %lld launches (%lld rules expanded, %lld pushed back), %.0f ms waiting on the "
-                     "GPU; host: %.0f ms launch prep (%.0f descriptors), %.0f ms result intake, %.0f ms commit, %.0f ms batch pops; %zu rules "
-                     "made\n",
-                     (long long)expansions, (long long)launches, (long long)gpu_rules, (long long)spec_pushback, wait_ms,
-                     prep_ms, fill_ms, post_ms, commit_ms, pop_ms, rp.st.size());
-    if (ctx->opts.verbose)
-        std::fprintf(stderr, "[fsm tsr] child speculation: %lld rules in %lld launches (%lld committed, %lld dropped); partial rows %.1f MB; domain sids "
-                     "%lld (row entries %lld), rows where the rule holds %lld, row entries walked %lld; "
-                     "rules on their parent's kept rows %lld (ring: %llu entries written, %lld early finishes); candidates sorted %zu, popped %zu\n",
-                     (long long)spec_made, (long long)spec_launches, (long long)spec_hit, (long long)spec_waste, double(exp_part_bytes) / 1e6, (long long)exp_domain,
-                     (long long)exp_entries, (long long)exp_hold, (long long)exp_walk, (long long)exp_plist,
-                     (unsigned long long)ahead, (long long)ring_waits, rp.cand.n_sorted, rp.cand.n_popped);
-    // ---------------- result = kRules
-    std::vector<const Rule*> res;
-    while (!rp.krules.empty()) {
-        res.push_back(rp.krules.top().r);
-        rp.krules.pop();
-    }
-    auto* o = static_cast<fsm_rules*>(std::calloc(1, sizeof(fsm_rules)));
-    if (!o) throw Error(FSM_ENOMEM, "calloc failed");
-    const size_t n = res.size();
-    o->n = int64_t(n);
-    o->total = d->N;
-    o->final_minsup = int32_t(rp.minsup);
-    size_t na = 0, nc = 0;
-    for (const Rule* r : res) { na += r->nx; nc += r->ny; }
-    o->support = static_cast<int32_t*>(std::malloc(std::max<size_t>(n, 1) * 4));
-    o->confidence = static_cast<double*>(std::malloc(std::max<size_t>(n, 1) * 8));
-    o->ante_off = static_cast<int64_t*>(std::malloc((n + 1) * 8));
-    o->cons_off = static_cast<int64_t*>(std::malloc((n + 1) * 8));
-    o->ante = static_cast<int32_t*>(std::malloc(std::max<size_t>(na, 1) * 4));
-    o->cons = static_cast<int32_t*>(std::malloc(std::max<size_t>(nc, 1) * 4));
-    if (!o->support || !o->confidence || !o->ante_off || !o->cons_off || !o->ante || !o->cons) {
-        fsm_rules_free(o);
-        throw Error(FSM_ENOMEM, "malloc failed");
-    }
-    o->ante_off[0] = o->cons_off[0] = 0;
-    for (size_t q = 0; q < n; ++q) {
-        const Rule* r = res[q];
-        o->support[q] = int32_t(r->sup);
-        o->confidence[q] = r->conf;
-        const uint32_t *rx = rp.st.X(r), *ry = rp.st.Y(r);
-        for (uint32_t x = 0; x < r->nx; ++x) o->ante[o->ante_off[q] + int64_t(x)] = db->tsr.item_val[rx[x]];
-        for (uint32_t x = 0; x < r->ny; ++x) o->cons[o->cons_off[q] + int64_t(x)] = db->tsr.item_val[ry[x]];
-        o->ante_off[q + 1] = o->ante_off[q] + int64_t(r->nx);
-        o->cons_off[q + 1] = o->cons_off[q] + int64_t(r->ny);
-    }
-    ctx->kstats.clear();
-    for (int q = 0; q < 4; ++q) {
-        if (!seg_name[q][0]) continue;
-        fsm_kernel_stat k{};
-        std::snprintf(k.name, sizeof(k.name), "%s", seg_name[q]);
-        k.launches = seg[q].n;
-        k.ms = seg[q].timed ? seg[q].ms * double(seg[q].n) / double(seg[q].timed) : 0.0;  // sampled, scaled
-        k.alg_bytes = seg[q].bytes;
-        k.survey_bytes = seg[q].survey;
-        ctx->kstats.push_back(k);
-    }
-    ctx->stats.exp_domain = exp_domain;
-    ctx->stats.exp_entries = exp_entries;
-    ctx->stats.exp_bitmap_bytes = exp_bitmap_bytes;
-    ctx->stats.expansions = expansions;
-    ctx->stats.rules = int64_t(n);
-    ctx->stats.ms_f2 = t1 - t0;          // pair phase
-    ctx->stats.ms_lattice = now_ms() - t1;  // expansions
-    ctx->stats.ms_count_kernel = wait_ms;   // of which: waiting for the expansion kernels
-    ctx->stats.count_launches = launches;
-    ctx->stats.ms_mine = now_ms() - t0;
+    TsrMiner mn(TsrKnobs::from_env(), ctx, db, k, minconf, t0);
+    mn.pair_phase();     // the valid rules of two items; minsup rises to the k-th best support
+    mn.keep_rows();      // the rows cut to the items that can still be in a rule: bitmap or list path
+    mn.size_launches();  // batch, passes, kept-row arena, memo
+    mn.alloc_sets();
+    mn.replay();         // launch / finish / speculate / commit until no candidate reaches minsup
+    mn.print_summary();
+    fsm_rules* o = mn.write_rules();
+    mn.write_stats(o->n);
     *out = o;
 }
 

@@ -185,6 +185,37 @@ def test_pair_phase_batch_edges(eng, env, monkeypatch):
     assert st["tight"]["exp_domain"] > 0
 
 
+# ------------------------------------------------------------ knobs are per mine
+def test_knobs_are_read_per_mine(fsm, eng, monkeypatch):
+    """One engine, one resident DB (family B, N = 1,023, tight mode), mined five times: default,
+    FSM_TSR_BATCH=1, default, FSM_TSR_MAX_KIDS=0, default.  Every mine sees the environment as it is
+    when it starts: one rule per launch takes more launches than the default batch, no kept item
+    allowed on the bitmap path reads no bitmap (the list path), and the default mines in between
+    are untouched by either (all their counters equal; the ms_* fields are clock readings)."""
+    db = E.tsr_window_cases()["N%d" % (E.tsr_constants()["exp_win"] - 1)]
+    mode, k, final = E.tsr_modes(db)[1]
+    o = tsr_ref(db, k)
+    assert o["final_minsup"] == final
+    h = eng.db_from_tokens(db.sids, db.seq_off, db.tokens, fsm.MODE_TSR)
+    stats = []
+    try:
+        for env in ("", "FSM_TSR_BATCH=1", "", "FSM_TSR_MAX_KIDS=0", ""):
+            with monkeypatch.context() as mp:
+                setenv(mp, env)
+                rules, meta = eng.tsr(h, k, db.minconf)
+            rules.sort(key=lambda t: (-t[2], t[0], t[1]))
+            assert rules == o["rules"], env
+            assert meta["final_minsup"] == final, env
+            stats.append({n: v for n, v in eng.stats().items() if not n.startswith("ms_")})
+    finally:
+        h.free()
+    default, batch1, default2, no_kids, default3 = stats
+    assert batch1["count_launches"] > default["count_launches"]
+    assert no_kids["exp_bitmap_bytes"] == 0
+    assert all(st["exp_bitmap_bytes"] > 0 for st in (default, batch1, default2, default3))
+    assert default == default2 == default3
+
+
 # ------------------------------------------------------------ F. in-process ranks
 @pytest.mark.parametrize("shard_min", ["0", ""], ids=["shard-every-launch", "shard-default"])
 @pytest.mark.parametrize("devices", [(0, 0), (0, 0, 0)], ids=lambda d: "ranks%d" % len(d))
