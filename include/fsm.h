@@ -305,6 +305,31 @@ int fsm_patterns_support(fsm_ctx* ctx, fsm_db* db, const fsm_patterns* in, int32
 int fsm_tsr_mine(fsm_ctx* ctx, fsm_db* db, int32_t k, double minconf, fsm_rules** out);
 void fsm_rules_free(fsm_rules* r);
 
+/* Support, antecedent count and confidence of GIVEN rules in a resident TSR DB, counted on
+ * the GPU by definition on the DB's rows (row = sequence).  For rule r = X => Y:
+ *   ante_out[r]       = number of rows holding every item of X
+ *   support_out[r]    = number of rows holding every item of X and of Y in which the latest
+ *                       first occurrence of an X item lies strictly before the earliest last
+ *                       occurrence of a Y item (max first_x < min last_y, itemset indexes)
+ *   confidence_out[r] = (double)support / (double)ante, the miner's own expression, so a
+ *                       mined rule scores bit-equal on its own DB; 0.0 when ante is 0
+ * ante_out and confidence_out may be NULL.  `in` is borrowed, never modified and may be
+ * caller-built: its support and confidence (either may be NULL), total and final_minsup are
+ * ignored, its items are item VALUES as in a mined result, and it is checked before any
+ * device work (ante_off / cons_off monotone from 0, every rule with a non-empty X and a
+ * non-empty Y, items strictly ascending inside a side, no item on both sides: FSM_EINVAL;
+ * n or the items over all rules >= 2^32 - 2: FSM_ELIMIT; a db not of FSM_MODE_TSR or of
+ * another context: FSM_EINVAL).  A failed check leaves the three outputs untouched.  An item
+ * the DB does not hold is not an error: in X it gives ante 0, support 0, confidence 0.0; in Y
+ * support 0 with ante still counted.  Equal rules are separate entries with equal results;
+ * n == 0 succeeds and writes nothing.  A side may be of any length (the miner's limit of 63
+ * items per side does not apply).  Nothing is built on the DB: the call reads its rows and
+ * the item -> sids lists it was made with.  A group context (ndevices > 1) counts on its rank
+ * 0's replica; with nranks > 1 each process counts on its own.  fsm_stats is left as it is;
+ * the kernel statistics become this call's (k_rs_count). */
+int fsm_rules_support(fsm_ctx* ctx, fsm_db* db, const fsm_rules* in, int32_t* support_out /* [in->n] */,
+                      int32_t* ante_out /* [in->n], may be NULL */, double* confidence_out /* [in->n], may be NULL */);
+
 /* Result persistence (SPADEActor.scala:47-68, TSRActor.scala:52-71): the
  * mined CSR rendered in bulk as the documents the actors hand to their sinks.
  *   fsm_patterns_serialize: one SPMF serialize() line per pattern,

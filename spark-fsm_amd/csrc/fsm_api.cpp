@@ -976,6 +976,26 @@ int fsm_patterns_support(fsm_ctx* ctx, fsm_db* db, const fsm_patterns* in, int32
     return guarded(ctx, [&] { fsm::patterns_support(ctx, db, in, support_out); });
 }
 
+int fsm_rules_support(fsm_ctx* ctx, fsm_db* db, const fsm_rules* in, int32_t* support_out, int32_t* ante_out,
+                      double* confidence_out) {
+    if (!ctx || !db || !in || !support_out) return fail(ctx, FSM_EINVAL, "null argument");
+    if (db->ctx != ctx) return fail(ctx, FSM_EINVAL, "db belongs to another context");
+    if (db->mode != FSM_MODE_TSR) return fail(ctx, FSM_EINVAL, "db was not flattened for TSR");
+    if (ctx->group) {
+        // rank 0's context and replica, on the calling thread, as fsm_patterns_support runs
+        fsm::Group& g = *ctx->group;
+        if (!g.ready()) return group_finish(ctx, fsm::Group::kStalled);
+        if (db->parts.empty() || !db->parts[0]) return fail(ctx, FSM_EINVAL, "db has no replica on rank 0");
+        fsm_ctx* r0 = g.ranks[0];
+        const int rc = fsm_rules_support(r0, db->parts[0], in, support_out, ante_out, confidence_out);
+        ctx->err = r0->err;
+        if (rc == FSM_OK) ctx->kstats = r0->kstats;
+        return rc;
+    }
+    // (nranks > 1: every process counts on its own replica; no collectives)
+    return guarded(ctx, [&] { fsm::rules_support(ctx, db, in, support_out, ante_out, confidence_out); });
+}
+
 // (result arrays may be big host blocks: fsm::big_give frees malloc'ed ones, caches the others)
 void fsm_patterns_free(fsm_patterns* p) {
     if (!p) return;

@@ -369,6 +369,10 @@ void pf_validate(const fsm_patterns* in, const char* who, bool need_support, std
                  std::vector<uint8_t>& start);
 // supports of given patterns in a resident SPADE DB (pattern_support.hip)
 void patterns_support(fsm_ctx* ctx, fsm_db* db, const fsm_patterns* in, int32_t* support_out);
+// support, antecedent count and confidence of given rules in a resident TSR DB (rule_support.hip);
+// ante_out and confidence_out may be null
+void rules_support(fsm_ctx* ctx, fsm_db* db, const fsm_rules* in, int32_t* support_out, int32_t* ante_out,
+                   double* confidence_out);
 // FSM_HOST_PROF=<file>: SIGPROF sampling of the host side of a mine (host_prof.cpp)
 bool host_prof_start();
 void host_prof_stop();

@@ -144,7 +144,7 @@ EXPORTS = [
     "fsm_db_free", "fsm_spade_mine", "fsm_patterns_free", "fsm_tsr_mine", "fsm_rules_free",
     "fsm_db_export", "fsm_db_image_free", "fsm_ingest", "fsm_token_db_free", "fsm_patterns_serialize",
     "fsm_patterns_json", "fsm_rules_json", "fsm_buffer_free", "fsm_rules_query", "fsm_patterns_filter",
-    "fsm_patterns_support",
+    "fsm_patterns_support", "fsm_rules_support",
 ]
 
 _lib = None
@@ -203,6 +203,8 @@ def load():
         L.fsm_patterns_filter.argtypes = [vp, P(Patterns), ctypes.c_int32, P(P(Patterns)), P(ctypes.c_int64)]
     if hasattr(L, "fsm_patterns_support"):
         L.fsm_patterns_support.argtypes = [vp, vp, P(Patterns), P(ctypes.c_int32)]
+    if hasattr(L, "fsm_rules_support"):
+        L.fsm_rules_support.argtypes = [vp, vp, P(Rules), P(ctypes.c_int32), P(ctypes.c_int32), P(ctypes.c_double)]
     _lib = L
     return L
 

@@ -97,6 +97,20 @@ def extract_rdd_rules(dataset, k, minconf, engine=None):
     return [Rule(x, y, s, c) for x, y, s, c in rules]
 
 
+def rule_supports(records_or_db, rules, engine=None):
+    """What GIVEN rules (Engine.rule_supports' forms) score in a dataset of (sid, spmf_line)
+    pairs, or in a TSR DB an engine already holds (an extension: the reference can only mine)
+    -> (support int32[n], ante int32[n], confidence float64[n])."""
+    if hasattr(records_or_db, "handle"):
+        return records_or_db.engine.rule_supports(records_or_db, rules)
+    eng = engine or default_engine()
+    db = eng.db_from_spmf(list(records_or_db), MODE_TSR)
+    try:
+        return eng.rule_supports(db, rules)
+    finally:
+        db.free()
+
+
 def spade_actor_patterns(patterns):
     """SPADEActor.train's mapping (SPADEActor.scala:47-58): serialize(), split on
     '|', support = trim.toInt, itemsets = split("-1") -> trim -> split(" ") -> toInt.

@@ -273,6 +273,32 @@ class Engine:
         check(self._L.fsm_tsr_mine(self._ctx, db.handle, int(k), float(minconf), ctypes.byref(out)), self._ctx)
         return MinedRules(self._L, out)
 
+    def rule_supports(self, db, rules):
+        """fsm_rules_support: what GIVEN rules score in a resident TSR DB, counted on the GPU
+        by definition -> (support int32[n], ante int32[n], confidence float64[n]); ante is the
+        number of sequences holding the whole antecedent, confidence support / ante (0.0 when
+        ante is 0).
+
+        rules is a list of (X, Y) tuples, a list of (X, Y, support, confidence) tuples as
+        Engine.tsr returns them, a MinedRules, or a 4-tuple (ante_off, ante, cons_off, cons)
+        of arrays (see rules_csr).  Items are item values, ascending inside a side, no item on
+        both sides; an item the DB does not hold scores 0, and a side may be of any length."""
+        P = ctypes.POINTER
+        if isinstance(rules, MinedRules):
+            keep, n, ref = rules, rules.n, rules._p  # the library's own struct, borrowed
+        else:
+            xo, xs, yo, ys = keep = rules_csr(rules)
+            n = len(xo) - 1
+            ref = ctypes.byref(_lib.Rules(n, None, None, xo.ctypes.data_as(P(ctypes.c_int64)),
+                                          xs.ctypes.data_as(P(ctypes.c_int32)), yo.ctypes.data_as(P(ctypes.c_int64)),
+                                          ys.ctypes.data_as(P(ctypes.c_int32)), 0, 0))
+        sup, ante, conf = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.float64)
+        check(self._L.fsm_rules_support(self._ctx, db.handle, ref, sup.ctypes.data_as(P(ctypes.c_int32)),
+                                        ante.ctypes.data_as(P(ctypes.c_int32)),
+                                        conf.ctypes.data_as(P(ctypes.c_double))), self._ctx)
+        del keep
+        return sup[:n], ante[:n], conf[:n]
+
     def kernel_stats(self):
         """[{name, launches, alg_bytes, survey_bytes, ms}] of the last mine or filter call (device time, HIP
         events; alg_bytes: the kernel's own layout, survey_bytes: SURVEY §8(d) units)."""
@@ -327,6 +353,33 @@ class MinedRules:
             return ctypes.string_at(out, n.value).decode("utf-8")
         finally:
             self._L.fsm_buffer_free(out)
+
+
+def rules_csr(rules):
+    """The accepted forms of a rule set -> (ante_off int64[n+1], ante int32, cons_off
+    int64[n+1], cons int32), the four arrays fsm_rules_support reads.  rules is a 4-tuple of
+    such arrays (or lists), a MinedRules, or a list of (X, Y) or (X, Y, support, confidence)
+    tuples (anything after Y is ignored)."""
+    flat = (np.ndarray, list)
+    if isinstance(rules, MinedRules):
+        rules = [r[:2] for r in rules.rules()]
+    if (isinstance(rules, tuple) and len(rules) == 4 and all(isinstance(a, flat) for a in rules)
+            and (len(rules[0]) == 0 or not hasattr(rules[0][0], "__len__"))):
+        xo, xs, yo, ys = rules
+    else:
+        xo, xs, yo, ys = [0], [], [0], []
+        for r in rules:
+            xs.extend(r[0])
+            ys.extend(r[1])
+            xo.append(len(xs))
+            yo.append(len(ys))
+    xo = np.ascontiguousarray(xo, np.int64)
+    yo = np.ascontiguousarray(yo, np.int64)
+    xs = np.ascontiguousarray(xs, np.int32)
+    ys = np.ascontiguousarray(ys, np.int32)
+    if len(xo) < 1 or len(xo) != len(yo):
+        raise ValueError("ante_off and cons_off must have the same n + 1 >= 1 entries")
+    return xo, xs, yo, ys
 
 
 class DB:
