@@ -302,6 +302,41 @@ int fsm_patterns_filter(fsm_ctx* ctx, const fsm_patterns* in, int32_t keep, fsm_
  * statistics become this call's (k_ps_*). */
 int fsm_patterns_support(fsm_ctx* ctx, fsm_db* db, const fsm_patterns* in, int32_t* support_out /* [in->n] */);
 
+/* The sequence ids of the rows that hold GIVEN patterns in a resident SPADE DB: the lists
+ * behind the counts of fsm_patterns_support, made on the GPU by the same containment test
+ * (SURVEY A.2).  Pattern p's ids are sid[off[p] .. off[p+1]): the distinct sequence ids, as
+ * the caller gave them to fsm_db_from_*, whose merged row contains p; strictly ascending
+ * inside a pattern, patterns in input order, so off[p+1] - off[p] is p's support.  A sequence
+ * id whose records hold no item is in no list.
+ * `in` is borrowed, never modified and may be caller-built, exactly as for
+ * fsm_patterns_support: its support (may be NULL), total and minsup are ignored, its items are
+ * item VALUES, and it is checked before any device work by the CSR rules of
+ * fsm_patterns_filter (FSM_EINVAL; n or n_items >= 2^32 - 2: FSM_ELIMIT; a db not of
+ * FSM_MODE_SPADE or of another context: FSM_EINVAL; a NULL argument: FSM_EINVAL).  A failed
+ * call leaves *out untouched.  A pattern that cannot match (an item the DB does not hold,
+ * more itemsets than the DB has eids, more items than any row) gets an empty list, not an
+ * error; equal patterns get separate, equal lists; n == 0 returns n = 0, off = {0},
+ * n_sids = 0.
+ * max_sids > 0 caps the ids over all patterns: a larger total returns FSM_ELIMIT with the
+ * total needed in the message, allocates nothing for the result and leaves *out untouched
+ * (the total is known after the match pass, before any id is written).  max_sids <= 0: no
+ * caller cap; a failed host allocation is FSM_ENOMEM.
+ * *out is a new library-owned result (fsm_sidlists_free).  The first call on a DB builds its
+ * item -> rows index if no fsm_patterns_support has, and puts the index lists in ascending row
+ * order (once per DB; a sort with 16 bytes per DB entry and its own scratch while it runs); the DB keeps the sequence ids
+ * of its rows (4 bytes per row on the host and, from this call on, on the device).  A group
+ * context (ndevices > 1) answers from its rank 0's replica; with nranks > 1 each process
+ * answers from its own.  fsm_stats is left as it is; the kernel statistics become this call's
+ * (k_ps_*). */
+typedef struct {
+    int64_t n;                  /* patterns (= in->n) */
+    int64_t* off;               /* [n+1], off[0] = 0 */
+    int32_t* sid;               /* [n_sids] */
+    int64_t n_sids;             /* off[n] */
+} fsm_sidlists;
+int fsm_patterns_sids(fsm_ctx* ctx, fsm_db* db, const fsm_patterns* in, int64_t max_sids, fsm_sidlists** out);
+void fsm_sidlists_free(fsm_sidlists* s);   /* NULL is a no-op */
+
 int fsm_tsr_mine(fsm_ctx* ctx, fsm_db* db, int32_t k, double minconf, fsm_rules** out);
 void fsm_rules_free(fsm_rules* r);
 

@@ -21,12 +21,16 @@ struct SpadeDevDB {
     int pos_state = 0;
     // the vertical index (pattern_support.hip): item i's entries are vert[vert_off[i] ..
     // vert_off[i+1]), each (row, entry index); made by the first fsm_patterns_support on this
-    // DB (vert_state 0 = not made, 1 = made), in no particular order inside a list.  The host
-    // copy of vert_off gives the list lengths (= F1 supports) the pivot choice reads
+    // DB (vert_state 0 = not made, 1 = made, in no particular order inside a list, 2 = made
+    // and every list in ascending row order: the first fsm_patterns_sids orders them).  The
+    // host copy of vert_off gives the list lengths (= F1 supports) the pivot choice reads
     fsm::DevBuf vert_off;  // u32 [U+1]
     fsm::DevBuf vert;      // uint2 [E]
     std::vector<uint32_t> vert_off_host;
     int vert_state = 0;
+    // the sequence id of every row (fsm_db::row_sid), uploaded by the first fsm_patterns_sids
+    fsm::DevBuf row_sid;   // i32 [R]
+    bool row_sid_made = false;
 };
 
 // TSR: horizontal rows (sid = row) of (item, first, last itemset index),

@@ -121,6 +121,24 @@ template <class T> T* host_copy(const fsm::DevBuf& d, size_t n, hipStream_t s) {
 
 int group_make_db(fsm_ctx* ctx, int32_t mode, const fsm::Source& src, fsm_db** out);
 
+// A SPADE DB keeps the sequence id of every row (fsm_patterns_sids returns them): both builds
+// make one row per distinct sequence id in ascending id order, a record without any item
+// included (its row is empty), so row r's id is the r-th distinct id of the input.
+void keep_row_sids(const fsm::Source& src, fsm_db* db) {
+    if (db->mode != FSM_MODE_SPADE) return;
+    std::vector<int32_t>& v = db->row_sid;
+    v.assign(src.sids, src.sids + src.n);
+    bool ascending = true;  // (K0 only takes strictly ascending ids)
+    for (int64_t r = 1; r < src.n && ascending; ++r) ascending = v[size_t(r)] > v[size_t(r - 1)];
+    if (!ascending) {
+        std::sort(v.begin(), v.end());
+        v.erase(std::unique(v.begin(), v.end()), v.end());
+    }
+    if (int64_t(v.size()) != db->spade_dev->R)
+        throw Error(FSM_EDEVICE, "SPADE DB: " + std::to_string(db->spade_dev->R) + " rows for " +
+                                     std::to_string(v.size()) + " distinct sequence ids");
+}
+
 int make_db(fsm_ctx* ctx, int32_t mode, const fsm::Source& src, fsm_db** out) {
     if (!ctx || !out) return fail(ctx, FSM_EINVAL, "null argument");
     *out = nullptr;
@@ -136,7 +154,10 @@ int make_db(fsm_ctx* ctx, int32_t mode, const fsm::Source& src, fsm_db** out) {
         ctx->stats.k0_device = 0;
         ctx->stats.db_parses = 1;  // this call's one pass over the caller's input
         ctx->stats.db_replicas = 0;
-        if (fsm::k0_build(ctx, mode, src, db)) return;  // K0 on the GPU (token input)
+        if (fsm::k0_build(ctx, mode, src, db)) {  // K0 on the GPU (token input)
+            keep_row_sids(src, db);
+            return;
+        }
         const double t0 = fsm::now_ms();
         if (mode == FSM_MODE_SPADE) fsm::flatten_spade(src, db->spade);
         else fsm::flatten_tsr(src, db->tsr);
@@ -154,6 +175,7 @@ int make_db(fsm_ctx* ctx, int32_t mode, const fsm::Source& src, fsm_db** out) {
         std::vector<uint32_t>().swap(db->tsr.ent_last);
         ctx->stats.ms_flatten = t1 - t0;
         ctx->stats.ms_upload = fsm::now_ms() - t1;
+        keep_row_sids(src, db);
     });
     if (rc != FSM_OK) {
         fsm_db_free(db);
@@ -489,6 +511,7 @@ int replicate_db(fsm_ctx* c, const fsm_db* src, fsm_db** out) {
             db->spade.W = src->spade.W;
             db->spade.max_occ = src->spade.max_occ;
             db->spade.item_val = src->spade.item_val;
+            db->row_sid = src->row_sid;
             db->spade_dev = d.release();
         } else {
             const TsrDevDB* a = src->tsr_dev;
@@ -974,6 +997,36 @@ int fsm_patterns_support(fsm_ctx* ctx, fsm_db* db, const fsm_patterns* in, int32
     }
     // (nranks > 1: every process counts on its own replica; no collectives)
     return guarded(ctx, [&] { fsm::patterns_support(ctx, db, in, support_out); });
+}
+
+int fsm_patterns_sids(fsm_ctx* ctx, fsm_db* db, const fsm_patterns* in, int64_t max_sids, fsm_sidlists** out) {
+    if (!ctx || !db || !in || !out) return fail(ctx, FSM_EINVAL, "null argument");
+    if (db->ctx != ctx) return fail(ctx, FSM_EINVAL, "db belongs to another context");
+    if (db->mode != FSM_MODE_SPADE) return fail(ctx, FSM_EINVAL, "db was not flattened for SPADE");
+    if (ctx->group) {
+        // rank 0's context and replica, on the calling thread, as fsm_patterns_support runs
+        fsm::Group& g = *ctx->group;
+        if (!g.ready()) return group_finish(ctx, fsm::Group::kStalled);
+        if (db->parts.empty() || !db->parts[0]) return fail(ctx, FSM_EINVAL, "db has no replica on rank 0");
+        fsm_ctx* r0 = g.ranks[0];
+        const int rc = fsm_patterns_sids(r0, db->parts[0], in, max_sids, out);
+        ctx->err = r0->err;
+        if (rc == FSM_OK) ctx->kstats = r0->kstats;
+        return rc;
+    }
+    // (nranks > 1: every process answers from its own replica; no collectives)
+    fsm_sidlists* res = nullptr;  // (*out is written on success only)
+    const int rc = guarded(ctx, [&] { fsm::patterns_sids(ctx, db, in, max_sids, &res); });
+    if (rc == FSM_OK) *out = res;
+    else fsm_sidlists_free(res);
+    return rc;
+}
+
+void fsm_sidlists_free(fsm_sidlists* s) {
+    if (!s) return;
+    fsm::big_give(s->off);
+    fsm::big_give(s->sid);
+    std::free(s);
 }
 
 int fsm_rules_support(fsm_ctx* ctx, fsm_db* db, const fsm_rules* in, int32_t* support_out, int32_t* ante_out,

@@ -348,6 +348,9 @@ struct fsm_db {
     std::shared_ptr<std::atomic<bool>> group_stuck;  // the group's stalled-rank flag (group DBs)
     fsm::FlatSpade spade;
     fsm::FlatTsr tsr;
+    // SPADE: the distinct sequence ids of the caller's records, ascending = the sequence id of
+    // every row (both builds keep one row per distinct id, empty rows included)
+    std::vector<int32_t> row_sid;
     SpadeDevDB* spade_dev = nullptr;
     TsrDevDB* tsr_dev = nullptr;
 };
@@ -369,6 +372,11 @@ void pf_validate(const fsm_patterns* in, const char* who, bool need_support, std
                  std::vector<uint8_t>& start);
 // supports of given patterns in a resident SPADE DB (pattern_support.hip)
 void patterns_support(fsm_ctx* ctx, fsm_db* db, const fsm_patterns* in, int32_t* support_out);
+// the sequence ids of the rows that hold given patterns (pattern_support.hip)
+void patterns_sids(fsm_ctx* ctx, fsm_db* db, const fsm_patterns* in, int64_t max_sids, fsm_sidlists** out);
+// n distinct keys (dense item id << 32 | entry index, item ids below 2^item_bits) in ascending
+// order: the DB entries by item, entries ascending inside an item (sparse_count.hip)
+void sort_entry_keys(const uint64_t* keys, uint64_t* sorted, uint64_t n, unsigned item_bits, hipStream_t s);
 // support, antecedent count and confidence of given rules in a resident TSR DB (rule_support.hip);
 // ante_out and confidence_out may be null
 void rules_support(fsm_ctx* ctx, fsm_db* db, const fsm_rules* in, int32_t* support_out, int32_t* ante_out,

@@ -26,4 +26,13 @@ void sparse_sort_rle(const uint64_t* keys, uint64_t* sorted, uint64_t n, unsigne
     FSM_HIP(rocprim::run_length_encode(tmp.p, t_rle, sorted, unsigned(n), uniq, counts, nruns, s));
 }
 
+// fsm_patterns_sids' list order (pattern_support.hip, ps_order_index): the bits of the entry
+// index (32) and of the item id above them
+void sort_entry_keys(const uint64_t* keys, uint64_t* sorted, uint64_t n, unsigned item_bits, hipStream_t s) {
+    size_t t_sort = 0;
+    FSM_HIP(rocprim::radix_sort_keys(nullptr, t_sort, keys, sorted, n, 0u, 32u + item_bits, s));
+    DevBuf tmp(std::max<size_t>(t_sort, 16));
+    FSM_HIP(rocprim::radix_sort_keys(tmp.p, t_sort, keys, sorted, n, 0u, 32u + item_bits, s));
+}
+
 }  // namespace fsm

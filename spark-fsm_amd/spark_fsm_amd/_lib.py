@@ -86,6 +86,15 @@ class Rules(ctypes.Structure):
     ]
 
 
+class SidLists(ctypes.Structure):
+    _fields_ = [
+        ("n", ctypes.c_int64),
+        ("off", ctypes.POINTER(ctypes.c_int64)),
+        ("sid", ctypes.POINTER(ctypes.c_int32)),
+        ("n_sids", ctypes.c_int64),
+    ]
+
+
 class DbImage(ctypes.Structure):
     _fields_ = [
         ("mode", ctypes.c_int32),
@@ -144,7 +153,7 @@ EXPORTS = [
     "fsm_db_free", "fsm_spade_mine", "fsm_patterns_free", "fsm_tsr_mine", "fsm_rules_free",
     "fsm_db_export", "fsm_db_image_free", "fsm_ingest", "fsm_token_db_free", "fsm_patterns_serialize",
     "fsm_patterns_json", "fsm_rules_json", "fsm_buffer_free", "fsm_rules_query", "fsm_patterns_filter",
-    "fsm_patterns_support", "fsm_rules_support",
+    "fsm_patterns_support", "fsm_rules_support", "fsm_patterns_sids", "fsm_sidlists_free",
 ]
 
 _lib = None
@@ -203,6 +212,10 @@ def load():
         L.fsm_patterns_filter.argtypes = [vp, P(Patterns), ctypes.c_int32, P(P(Patterns)), P(ctypes.c_int64)]
     if hasattr(L, "fsm_patterns_support"):
         L.fsm_patterns_support.argtypes = [vp, vp, P(Patterns), P(ctypes.c_int32)]
+    if hasattr(L, "fsm_patterns_sids"):
+        L.fsm_patterns_sids.argtypes = [vp, vp, P(Patterns), ctypes.c_int64, P(P(SidLists))]
+        L.fsm_sidlists_free.argtypes = [P(SidLists)]
+        L.fsm_sidlists_free.restype = None
     if hasattr(L, "fsm_rules_support"):
         L.fsm_rules_support.argtypes = [vp, vp, P(Rules), P(ctypes.c_int32), P(ctypes.c_int32), P(ctypes.c_double)]
     _lib = L

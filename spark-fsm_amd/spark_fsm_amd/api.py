@@ -86,6 +86,23 @@ def pattern_supports(records_or_db, patterns, engine=None):
         db.free()
 
 
+def pattern_sids(records_or_db, patterns, engine=None):
+    """The sequence ids in which GIVEN patterns (Engine.pattern_supports' forms) occur, in a
+    dataset of (sid, spmf_line) pairs or in a SPADE DB an engine already holds (SPMF's "show
+    sequence identifiers") -> one ascending list of ids per pattern."""
+    if hasattr(records_or_db, "handle"):
+        off, sid = records_or_db.engine.pattern_sids(records_or_db, patterns)
+    else:
+        eng = engine or default_engine()
+        db = eng.db_from_spmf(list(records_or_db), MODE_SPADE)
+        try:
+            off, sid = eng.pattern_sids(db, patterns)
+        finally:
+            db.free()
+    off, sid = off.tolist(), sid.tolist()
+    return [sid[off[p]:off[p + 1]] for p in range(len(off) - 1)]
+
+
 def extract_rdd_rules(dataset, k, minconf, engine=None):
     """TSR.extractRDDRules (TSR.scala:31-107) on the GPU engine."""
     eng = engine or default_engine()

@@ -171,15 +171,13 @@ class Engine:
                              len(so) - 1, len(it), 0, 0)
         return self._filter(pats, keep, copy)
 
-    def pattern_supports(self, db, patterns):
-        """fsm_patterns_support: the supports of GIVEN patterns in a resident SPADE DB,
-        counted on the GPU by definition -> np.ndarray[int32], one count per pattern.
-
-        patterns is a CSR tuple (support_or_None, pat_off, set_off, items) like spade_csr's
-        (the supports are ignored), or a list of itemset tuples such as ((1,), (3, 4)), or
-        a list of (itemsets, support) pairs as Engine.spade returns them.  Items are item
-        values; a pattern that cannot match (an unknown item, more itemsets than the DB
-        has eids) counts 0.  The first call on a DB builds its item -> rows index."""
+    @staticmethod
+    def _patterns_arg(patterns):
+        """The accepted forms of a GIVEN pattern set -> (_lib.Patterns, n, keep): a CSR tuple
+        (support_or_None, pat_off, set_off, items) like spade_csr's (the supports are
+        ignored), a list of itemset tuples such as ((1,), (3, 4)), or a list of (itemsets,
+        support) pairs as Engine.spade returns them.  keep holds the arrays the struct
+        points into."""
         flat = (np.ndarray, list)
         if (isinstance(patterns, tuple) and len(patterns) == 4 and (patterns[0] is None or isinstance(patterns[0], flat))
                 and isinstance(patterns[1], flat) and (len(patterns[1]) == 0 or not hasattr(patterns[1][0], "__len__"))):
@@ -202,11 +200,46 @@ class Engine:
         P = ctypes.POINTER
         pats = _lib.Patterns(n, None, po.ctypes.data_as(P(ctypes.c_int64)), so.ctypes.data_as(P(ctypes.c_int64)),
                              it.ctypes.data_as(P(ctypes.c_int32)), len(so) - 1, len(it), 0, 0)
+        return pats, n, (po, so, it)
+
+    def pattern_supports(self, db, patterns):
+        """fsm_patterns_support: the supports of GIVEN patterns in a resident SPADE DB,
+        counted on the GPU by definition -> np.ndarray[int32], one count per pattern.
+
+        patterns is a CSR tuple (support_or_None, pat_off, set_off, items) like spade_csr's
+        (the supports are ignored), or a list of itemset tuples such as ((1,), (3, 4)), or
+        a list of (itemsets, support) pairs as Engine.spade returns them.  Items are item
+        values; a pattern that cannot match (an unknown item, more itemsets than the DB
+        has eids) counts 0.  The first call on a DB builds its item -> rows index."""
+        pats, n, keep = self._patterns_arg(patterns)
         out = np.zeros(n, np.int32)
         buf = out if n else np.zeros(1, np.int32)
         check(self._L.fsm_patterns_support(self._ctx, db.handle, ctypes.byref(pats),
-                                           buf.ctypes.data_as(P(ctypes.c_int32))), self._ctx)
+                                           buf.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))), self._ctx)
+        del keep
         return out
+
+    def pattern_sids(self, db, patterns, max_sids=0, copy=False):
+        """fsm_patterns_sids: the sequence ids of the rows that hold GIVEN patterns in a
+        resident SPADE DB -> (off int64[n + 1], sid int32[n_sids]); pattern p's ids are
+        sid[off[p]:off[p + 1]], strictly ascending, as the DB's records named them, so
+        np.diff(off) are the supports.
+
+        patterns takes the forms of pattern_supports; a pattern that cannot match gets an
+        empty list.  max_sids > 0 caps the ids over all patterns: a larger result raises
+        FsmError (FSM_ELIMIT, the total needed in its message) before anything is
+        allocated for it.  The arrays are read-only views of the library's result with
+        spade_csr's ownership rules; copy=True returns independent, writable copies.  The
+        first call on a DB orders its item -> rows index."""
+        pats, _n, keep = self._patterns_arg(patterns)
+        out = ctypes.POINTER(_lib.SidLists)()
+        check(self._L.fsm_patterns_sids(self._ctx, db.handle, ctypes.byref(pats), int(max_sids), ctypes.byref(out)),
+              self._ctx)
+        del keep
+        owner = _ResultOwner(self._L.fsm_sidlists_free, out)
+        r = out.contents
+        res = (owner.view(r.off, r.n + 1, np.int64), owner.view(r.sid, r.n_sids, np.int32))
+        return tuple(a.copy() for a in res) if copy else res
 
     def spade_csr(self, db, support, dfs=True, copy=False, keep="all"):
         """fsm_spade_mine -> CSR numpy arrays (support, pat_off, set_off, items), meta.
