@@ -19,6 +19,12 @@ struct SpadeDevDB {
     // -1 = a row exceeds 65535 entries (that DB keeps the root slab)
     fsm::DevBuf pos;      // u32 [E]
     int pos_state = 0;
+    // the bounded root F2 plan's table (spade_engine.hip, k_f2_bound_tab): per row block b and
+    // item u the sum of 1 + 3 (entries after it in its row) over u's entries in b, made by the
+    // first mine that takes the bounded plan; f2_bound_rpb = the rows per block it was built
+    // for (0 = not made; rebuilt when a mine's row block geometry differs)
+    fsm::DevBuf f2_bound;  // u32 [row blocks * U]
+    uint32_t f2_bound_rpb = 0;
     // the vertical index (pattern_support.hip): item i's entries are vert[vert_off[i] ..
     // vert_off[i+1]), each (row, entry index); made by the first fsm_patterns_support on this
     // DB (vert_state 0 = not made, 1 = made, in no particular order inside a list, 2 = made

@@ -17,7 +17,9 @@
 //   root           the root class is the flattened DB restricted to the frequent items.
 //                  DB-direct (default): no root slab, k_db_pos (row positions, once per
 //                  DB) and k_f2_plan_db (key capacities per rank group and row block)
-//                  read the DB rows.  Slab root: k_root_count + k_root_write_plan (or
+//                  read the DB rows; unsharded W = 1 roots bound the capacities from a
+//                  per-DB table instead (k_f2_bound_tab once, k_f2_plan_bound + k_mem_db
+//                  per mine).  Slab root: k_root_count + k_root_write_plan (or
 //                  k_root_write when the F2 geometry does not apply) write the slab.
 //   root F2        the F x 2F pair matrix, by far the largest: one enumeration writes
 //                  every entry's pair keys into its rank group's region (k_f2_tri:
@@ -36,7 +38,8 @@
 //                  batches in one pass (k_freq_recs), large ones in row order
 //                  (k_freq_count, k_freq_write, with the kid table from k_kid_off).
 //   k_rk_*         a one-group batch's records ordered by (row, slot) on the device,
-//                  with the kid and child-class tables (hist, tables, scatter, row).
+//                  with the kid and child-class tables (hist, tables, scatter, row); a
+//                  lattice batch's behind k_freq_recs, before its count is read (tables, run).
 //   emit           (entry, frequent child) pairs: find the partner entry in the
 //                  (member-sorted) run, write the child runs at a slab cursor.  k_emit2
 //                  (windows of whole runs in registers; W <= 8) hands its long runs to
@@ -697,6 +700,97 @@ __global__ __launch_bounds__(kF2Threads) void k_f2_plan_db(const uint32_t* __res
     for (uint32_t g = threadIdx.x; g < G; g += blockDim.x) cap[f2_region(g, blockIdx.x, nblk)] = (h[g] + amask) & ~amask;
 }
 
+// The static part of that plan (unordered-pair layout, unsharded), once per DB: S[b][u] = the
+// sum over item u's entries in row block b of 1 + 3 (entries after it in its row).  Rows are
+// item-sorted and ranks ascend with the item, so whatever the minsup an entry's frequent
+// partners after it are at most the entries after it: S bounds the exact capacity item by
+// item.  (An item occurs once per row and rows hold at most 65535 entries: a sum over the at
+// most kF2MaxRows rows of a block stays below 2^32.)  LDS counters when the items fit (k_f1's
+// bound), else global atomics on the zeroed table.
+__global__ __launch_bounds__(kBlock) void k_f2_bound_tab(const uint32_t* __restrict__ row_off,
+                                                         const uint32_t* __restrict__ item, uint32_t R, uint32_t rpb,
+                                                         uint32_t U, uint32_t* __restrict__ S, int use_lds) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t h[];
+    uint32_t* out = S + size_t(blockIdx.x) * U;
+    if (use_lds) {
+        for (uint32_t u = threadIdx.x; u < U; u += blockDim.x) h[u] = 0;
+        __syncthreads();
+    }
+    const uint32_t r0 = blockIdx.x * rpb, r1 = min(R, r0 + rpb);
+    for (uint32_t r = r0 + (threadIdx.x >> 6); r < r1; r += kBlock / 64) {
+        const uint32_t rb = row_off[r], e1 = row_off[r + 1];
+        for (uint32_t e = rb + lane_id(); e < e1; e += 64) {
+            const uint32_t w = 1u + 3u * (e1 - 1u - e);
+            if (use_lds) atomicAdd(&h[item[e]], w);
+            else atomicAdd(&out[item[e]], w);
+        }
+    }
+    if (use_lds) {
+        __syncthreads();
+        for (uint32_t u = threadIdx.x; u < U; u += blockDim.x) out[u] = h[u];
+    }
+}
+// The bounded plan of a mine: block b sums its row of S over the frequent items of each rank
+// group (ig[u]: item u's group, kNone for an infrequent item; the host makes it with the
+// group table, so a step is two independent coalesced loads) into cap[f2_region(g, b)],
+// aligned as k_f2_plan_db aligns them.  Groups are contiguous rank ranges and ranks ascend
+// with the item, so the 64 items of a wave step mostly share one group: one LDS atomic per
+// step then, per lane only where a group boundary falls inside the step.  A sum at 2^32 and
+// above saturates (the slot total then exceeds the limit and the exact plan runs).
+__global__ __launch_bounds__(kF2Threads) void k_f2_plan_bound(const uint32_t* __restrict__ S,
+                                                              const uint32_t* __restrict__ ig, uint32_t U, uint32_t G,
+                                                              uint32_t nblk, uint32_t* __restrict__ cap,
+                                                              uint32_t amask) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long hb[];
+    for (uint32_t g = threadIdx.x; g < G; g += blockDim.x) hb[g] = 0;
+    __syncthreads();
+    const uint32_t* row = S + size_t(blockIdx.x) * U;
+    const uint32_t lane = lane_id();
+    for (uint32_t u0 = threadIdx.x & ~63u; u0 < U; u0 += kF2Threads) {  // (wave-uniform)
+        const uint32_t u = u0 + lane;
+        const uint32_t g = u < U ? ig[u] : kNone;
+        const unsigned long long x = u < U ? row[u] : 0u;
+        const bool fr = g != kNone;
+        const uint64_t fb = ballot(fr);
+        if (!fb) continue;
+        const uint32_t g0 = __shfl(g, __builtin_ctzll(fb), 64);
+        if (ballot(fr && g != g0) == 0) {
+            const unsigned long long sum = wave_incl_scan(fr ? x : 0ull);
+            if (lane == 63) atomicAdd(&hb[g0], sum);
+        } else if (fr) {
+            atomicAdd(&hb[g], x);
+        }
+    }
+    __syncthreads();
+    for (uint32_t g = threadIdx.x; g < G; g += blockDim.x) {
+        const unsigned long long t = (hb[g] + amask) & ~(unsigned long long)amask;
+        cap[f2_region(g, blockIdx.x, nblk)] = t > 0xFFFFFFF8ull ? 0xFFFFFFF8u : uint32_t(t);
+    }
+}
+// the DB entries' member ids rk2[item] (k_f2_plan_db writes them on its way): four per thread
+// and step.  A few blocks per CU each stage rk2 in LDS when the items fit (k_f1's bound): the
+// four gathers of a step are LDS reads then, not 256 divergent cache requests per wave.
+__global__ __launch_bounds__(kF2Threads) void k_mem_db(const uint32_t* __restrict__ item,
+                                                       const uint32_t* __restrict__ rk2, uint32_t U, uint64_t E,
+                                                       uint32_t* __restrict__ mem, int use_lds) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t srk[];
+    if (use_lds) {
+        for (uint32_t u = threadIdx.x; u < U; u += blockDim.x) srk[u] = rk2[u];
+        __syncthreads();
+    }
+    const uint64_t n4 = E / 4, step = uint64_t(gridDim.x) * blockDim.x;
+    const uint64_t t = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    auto run = [&](const uint32_t* tab) {  // (inlined twice: LDS reads, or global loads)
+        for (uint64_t i = t; i < n4; i += step) {
+            const uint4 it = reinterpret_cast<const uint4*>(item)[i];
+            reinterpret_cast<uint4*>(mem)[i] = make_uint4(tab[it.x], tab[it.y], tab[it.z], tab[it.w]);
+        }
+        if (t < E - n4 * 4) mem[n4 * 4 + t] = tab[item[n4 * 4 + t]];
+    };
+    if (use_lds) run(srk);
+    else run(rk2);
+}
+
 // kRoot: the rows are the DB's (row_off32), entries read through rr (DB-direct root)
 template <int W, bool kRoot>
 __global__ __launch_bounds__(kF2Threads) void k_f2_keys(const uint64_t* __restrict__ roff,
@@ -1328,10 +1422,15 @@ __global__ __launch_bounds__(kBlock) void k_kid_off(const DRow* __restrict__ row
 // candidates and appends FreqRec{row, slot, sup} at a block cursor reserved with
 // one global atomic per block (unordered; the host orders them, order_recs).
 // More than `cap` records: only counted (the host retries with the exact size).
+// A row's records are one contiguous run in ascending slot order; with rowcnt, lane 0 of
+// every row's wave (empty rows too: nothing is zeroed first) also stores the row's true
+// count | kRkEven and, at rowcnt[nrows + g], where its run starts, for k_rk_run.
+constexpr uint32_t kRkEven = 1u << 31;  // rowcnt[r]: one of the row's records has an even slot (a sequence extension)
 __global__ __launch_bounds__(kBlock) void k_freq_recs(const DRow* __restrict__ rows, uint32_t nrows,
                                                       const DClass* __restrict__ cls, const uint32_t* __restrict__ cnt,
                                                       uint32_t minsup, uint32_t row_base, FreqRec* __restrict__ out,
-                                                      uint32_t cap, uint32_t* __restrict__ nout) {
+                                                      uint32_t cap, uint32_t* __restrict__ nout,
+                                                      uint32_t* __restrict__ rowcnt) {
     __shared__ uint32_t w_n[kBlock / 64];
     __shared__ uint32_t b_at;
     const uint32_t g = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -1341,13 +1440,16 @@ __global__ __launch_bounds__(kBlock) void k_freq_recs(const DRow* __restrict__ r
     DClass c{0, 0, 0, 0, 0, {0, 0}};
     const uint32_t* base = cnt;
     uint32_t n = 0;
+    uint64_t even = 0;  // (even lanes hold even slots: s0 is a multiple of 64)
     if (live) {
         r = rows[g];
         c = cls[r.cls];
         base = cnt + c.cnt_off + uint64_t(r.mi >> c.mshift) * c.rstride;
         for (uint32_t s0 = 0; s0 < c.D; s0 += 64) {
             const uint32_t slot = s0 + lane;
-            n += uint32_t(__popcll(ballot(slot < c.D && base[slot] >= minsup)));
+            const uint64_t fb = ballot(slot < c.D && base[slot] >= minsup);
+            n += uint32_t(__popcll(fb));
+            even |= fb & 0x5555555555555555ull;
         }
     }
     if (lane == 0) w_n[wv] = n;
@@ -1358,9 +1460,14 @@ __global__ __launch_bounds__(kBlock) void k_freq_recs(const DRow* __restrict__ r
         b_at = tot ? atomicAdd(nout, tot) : 0u;
     }
     __syncthreads();
-    if (!live || n == 0) return;
+    if (!live) return;
     uint32_t at = b_at;
     for (uint32_t k = 0; k < wv; ++k) at += w_n[k];
+    if (rowcnt && lane == 0) {
+        rowcnt[g] = n | (even ? kRkEven : 0u);
+        rowcnt[nrows + g] = at;
+    }
+    if (n == 0) return;
     for (uint32_t s0 = 0; s0 < c.D; s0 += 64) {
         const uint32_t slot = s0 + lane;
         const uint32_t v = slot < c.D ? base[slot] : 0u;
@@ -2156,8 +2263,7 @@ __device__ uint32_t rk_scan_range(uint32_t m, uint32_t* wsum, Get get, Put put) 
     }
     return tot;
 }
-// rowcnt[r]: the row's records | 1 << 31 if one of them has an even slot (a sequence extension)
-constexpr uint32_t kRkEven = 1u << 31;
+// rowcnt[r]: the row's records | kRkEven if one of them has an even slot (a sequence extension)
 __global__ __launch_bounds__(kBlock) void k_rk_hist(const FreqRec* __restrict__ R, uint32_t n,
                                                     FreqRec* __restrict__ Rd, uint32_t* __restrict__ rowcnt) {
     for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += gridDim.x * blockDim.x) {
@@ -2289,6 +2395,39 @@ __global__ __launch_bounds__(kBlock) void k_rk_row(const FreqRec* __restrict__ R
         kcid[beg + rank] = rec.cid;
     }
 }
+// The row kernel over k_freq_recs' runs (one wave per counter row): row r's records lie at
+// Rd[at, at + c) in ascending slot order already (rowcnt[r] = c | kRkEven, rowcnt[nrows + r]
+// = at), so a record's rank is its index in the run and its child member rank the distinct
+// partner items (slot >> 1) before it: no bitmap, no bucket index.  Launched before the
+// host knows the record count: a run or a row offset that reaches past cap (the extraction
+// overflowed; the host drops this pass and retries) is left alone.
+__global__ __launch_bounds__(kBlock) void k_rk_run(const FreqRec* __restrict__ Rd, const uint32_t* __restrict__ rowcnt,
+                                                   const uint32_t* __restrict__ rowoff, uint32_t nrows, uint32_t cap,
+                                                   FreqRec* __restrict__ out, uint32_t* __restrict__ kslot,
+                                                   uint32_t* __restrict__ kcid) {
+    const uint32_t r = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = lane_id();
+    if (r >= nrows) return;  // (wave-uniform, as everything below up to the loop body)
+    const uint32_t c = rowcnt[r] & ~kRkEven, at = rowcnt[nrows + r], beg = rowoff[r];
+    if (c == 0 || uint64_t(at) + c > cap || uint64_t(beg) + c > cap) return;
+    uint32_t crank = 0, last = kNone;  // partner items before this step, the last one's
+    for (uint32_t i0 = 0; i0 < c; i0 += 64) {
+        const uint32_t i = i0 + lane;
+        const bool in = i < c;
+        FreqRec rec = in ? Rd[at + i] : FreqRec{0, 0, 0, 0};
+        const uint32_t item = rec.slot >> 1;
+        uint32_t before = __shfl_up(item, 1, 64);
+        if (lane == 0) before = last;
+        const uint64_t lead = ballot(in && item != before);
+        if (in) {
+            rec.cid = (crank + uint32_t(__popcll(lead & (lanemask_lt() | 1ull << lane))) - 1u) << 1 | (rec.slot & 1u);
+            out[beg + i] = rec;
+            kslot[beg + i] = rec.slot;
+            kcid[beg + i] = rec.cid;
+        }
+        crank += uint32_t(__popcll(lead));
+        last = __shfl(item, 63, 64);
+    }
+}
 
 // ------------------------------------------------------------- host side
 
@@ -2327,6 +2466,9 @@ template <class F> void with_window_width(int W, F&& f) {
 //   FSM_ROOT_PATH     atomic: the root F2 by global atomics
 //   FSM_ROOT_DB       0: keep the root slab (k_root_count + k_root_write)
 //   FSM_F2_TRI        0: the ordered-pair root F2 (k_f2_keys) instead of k_f2_tri
+//   FSM_F2_PLAN       exact: the root F2 plan walked from the DB rows every mine (k_f2_plan_db);
+//                     bound (default): summed from the DB's table (unsharded W = 1 unordered-pair roots)
+//   FSM_F2_TAB_MAX    size guard of that table in bytes (256 MiB; a test hook: 0 forces the exact plan)
 //   FSM_F2_BLOCKS     target row blocks of the root F2, [1, kF2MaxBlocks] (1024)
 //   FSM_COUNT_KERNEL  thread: k_count for every batch (default: k_count2 where W has it)
 //   FSM_COUNT_CHUNK   class entries per k_count block, [256, 2^20] (kChunk)
@@ -2337,6 +2479,7 @@ template <class F> void with_window_width(int W, F&& f) {
 //   FSM_EMIT_GRID     grid cap of the emit kernels, [256, 2^22] (2^16)
 //   FSM_EMIT_DEFER    0: children built before the emit launch
 //   FSM_DEVORDER      0: a batch's records ordered on the host
+//   FSM_FREQ_CAP      test hook: caps the first record buffer of the one-pass extraction (the retry path)
 //   FSM_HOST_PAR_MIN  records from which the host tables are built by the thread pool, >= 1 (2^16)
 //   FSM_SPLIT_FRAC    sharded: a first-level class above this fraction of a rank's fair share
 //                     is split (0.5; <= 0: never)
@@ -2350,6 +2493,8 @@ struct SpadeKnobs {
     CountPath count_path;
     uint64_t keyed_min;
     bool root_atomic, root_db, f2_tri;
+    bool f2_bound;
+    uint64_t f2_tab_max;
     uint32_t f2_blocks;
     bool count_window;  // k_count2 where the width has it
     uint32_t count_chunk;
@@ -2359,6 +2504,7 @@ struct SpadeKnobs {
     uint32_t emit2_cap, emit1_cap;
     uint64_t emit_grid;
     bool emit_defer, devorder;
+    uint32_t freq_cap;  // (0: none)
     uint64_t host_par_min;
     double split_frac;  // (1e300: never split)
     bool claims, claims_forced;
@@ -2385,6 +2531,8 @@ struct SpadeKnobs {
         k.root_atomic = is("FSM_ROOT_PATH", "atomic");
         k.root_db = !lead("FSM_ROOT_DB", '0');
         k.f2_tri = !lead("FSM_F2_TRI", '0');
+        k.f2_bound = !is("FSM_F2_PLAN", "exact");
+        k.f2_tab_max = num("FSM_F2_TAB_MAX", uint64_t(256) << 20);
         k.f2_blocks = uint32_t(clamped("FSM_F2_BLOCKS", 1, kF2MaxBlocks, 1024));
         k.count_window = !is("FSM_COUNT_KERNEL", "thread");
         k.count_chunk = uint32_t(clamped("FSM_COUNT_CHUNK", 256, 1u << 20, kChunk));
@@ -2396,6 +2544,7 @@ struct SpadeKnobs {
         k.emit_grid = clamped("FSM_EMIT_GRID", 256, 1u << 22, 1u << 16);
         k.emit_defer = !lead("FSM_EMIT_DEFER", '0');
         k.devorder = !lead("FSM_DEVORDER", '0');
+        k.freq_cap = uint32_t(std::min<uint64_t>(num("FSM_FREQ_CAP", 0), kNone));
         k.host_par_min = std::max<uint64_t>(1, num("FSM_HOST_PAR_MIN", uint64_t(1) << 16));
         const char* sf = std::getenv("FSM_SPLIT_FRAC");
         const double f = sf ? std::atof(sf) : 0.5;
@@ -2595,7 +2744,7 @@ struct BatchRootF2 {
     // DB-direct root (no root slab): its kernels read the DB rows through rk2 (dense item ->
     // member id, odd for an infrequent item)
     DevBuf rk2;
-    DevBuf mem_db;  // u32 [DB entries]: each DB entry's member id rk2[item] (written by the F2 plan)
+    DevBuf mem_db;  // u32 [DB entries]: each DB entry's member id rk2[item] (the exact F2 plan, or k_mem_db behind the bounded one)
 };
 // sharded root with work stealing: children [0, nshared) are the heavy
 // classes every rank mines; the rest, largest first, are claimed in ranges from the
@@ -3317,15 +3466,45 @@ struct Miner {
     // is sized by every record's support (the lone itemset extensions' entries are counted out
     // when the children are built).  rr: the counter rows (nrows), dmax: the largest member id
     // space of a row's class.  false: the host orders them (sharded, claims, over budget).
-    bool order_device(Batch& b, PinnedBuf* pb, uint32_t nrec, uint32_t nrows, RkRows rr, uint32_t dmax, size_t nko) {
-        if (comm || nrec == 0 || nrows == 0 || !knobs.devorder || !knobs.emit_defer || b.claim.key >= 0 ||
-            dmax >= (1u << 16) || nko >= kNone)
-            return false;
-        const FreqRec* hr = static_cast<const FreqRec*>(pb->host);
-        uint64_t sumsup = 0;
+    // order_device's test in two parts: what is known before the records exist (so that
+    // extract_one_pass can launch the ordering behind k_freq_recs), and the budget of the
+    // deferred emit from the records' supports (ordered or not: a sum)
+    bool order_device_applies(const Batch& b, uint32_t nrows, uint32_t dmax, size_t nko) const {
+        return !comm && nrows != 0 && knobs.devorder && knobs.emit_defer && b.claim.key < 0 && dmax < (1u << 16) &&
+               nko < kNone;
+    }
+    bool order_device_fits(const FreqRec* hr, uint32_t nrec, uint32_t dmax, uint64_t& sumsup) const {
+        sumsup = 0;
         for (uint32_t q = 0; q < nrec; ++q) sumsup += hr[q].sup;
         // a row's c records give its child class D <= 2c <= 2 dmax members: sum (2c)^2 4 B <= 16 nrec dmax
-        if (sumsup * entry_bytes() + 16ull * nrec * dmax > budget || sumsup > (uint64_t(1) << 31)) return false;
+        return sumsup * entry_bytes() + 16ull * nrec * dmax <= budget && sumsup <= (uint64_t(1) << 31);
+    }
+    // the batch takes the device-ordered records hr[0, nrec) (in pinned memory at b.gpu.rec_ev)
+    // and the tables in b.gpu.kid_tab [koff: nko | kslot | kcid at kslot + stride]
+    void order_device_adopt(Batch& b, const FreqRec* hr, uint32_t nrec, uint64_t sumsup, size_t nko, size_t stride) {
+        b.gpu.kid_off = b.gpu.kid_tab.as<uint32_t>();
+        b.gpu.kid_slot = b.gpu.kid_off + nko;
+        b.gpu.kid_cid = b.gpu.kid_slot + stride;
+        b.defer.child_of = b.gpu.ord_child_of.as<uint32_t>();
+        b.dev_order = true;
+        b.defer.on = true;
+        b.defer.R = hr;
+        b.defer.n = nrec;
+        b.defer.total = sumsup;  // (an upper bound: emit() counts the children's entries exactly)
+        b.defer.rows = &rows_s;
+        b.children.clear();
+        b.groups.assign(1, {size_t(0), size_t(0)});  // (the child count: set by emit())
+        b.next_group = 0;
+    }
+    void record_rec_ev(Batch& b) {
+        if (!b.gpu.rec_ev.ev) FSM_HIP(hipEventCreateWithFlags(&b.gpu.rec_ev.ev, hipEventDisableTiming));
+        FSM_HIP(hipEventRecord(b.gpu.rec_ev.ev, s));
+    }
+    bool order_device(Batch& b, PinnedBuf* pb, uint32_t nrec, uint32_t nrows, RkRows rr, uint32_t dmax, size_t nko) {
+        if (nrec == 0 || !order_device_applies(b, nrows, dmax, nko)) return false;
+        const FreqRec* hr = static_cast<const FreqRec*>(pb->host);
+        uint64_t sumsup = 0;
+        if (!order_device_fits(hr, nrec, dmax, sumsup)) return false;
         const uint32_t n = nrec;
         FreqRec* R = static_cast<FreqRec*>(pb->dev);
         DevBuf Rd(size_t(n) * sizeof(FreqRec)), rowcnt(size_t(nrows) * 4), rowoff(size_t(nrows + 1) * 4),
@@ -3351,21 +3530,8 @@ struct Miner {
         hipLaunchKernelGGL(k_rk_row, dim3(nrows), dim3(kBlock), lds, s, Rd.as<FreqRec>(), idx.as<uint32_t>(),
                            rowoff.as<uint32_t>(), rr, nwmax, R, koff + nko, koff + nko + n);
         FSM_LAUNCHED("k_rk_row", s);
-        if (!b.gpu.rec_ev.ev) FSM_HIP(hipEventCreateWithFlags(&b.gpu.rec_ev.ev, hipEventDisableTiming));
-        FSM_HIP(hipEventRecord(b.gpu.rec_ev.ev, s));
-        b.gpu.kid_off = b.gpu.kid_tab.as<uint32_t>();
-        b.gpu.kid_slot = b.gpu.kid_off + nko;
-        b.gpu.kid_cid = b.gpu.kid_slot + n;
-        b.defer.child_of = b.gpu.ord_child_of.as<uint32_t>();
-        b.dev_order = true;
-        b.defer.on = true;
-        b.defer.R = hr;
-        b.defer.n = nrec;
-        b.defer.total = sumsup;  // (an upper bound: emit() counts the children's entries exactly)
-        b.defer.rows = &rows_s;
-        b.children.clear();
-        b.groups.assign(1, {size_t(0), size_t(0)});  // (the child count: set by emit())
-        b.next_group = 0;
+        record_rec_ev(b);
+        order_device_adopt(b, hr, nrec, sumsup, nko, n);
         return true;
     }
 
@@ -3781,38 +3947,78 @@ struct Miner {
         if (ride) dn = reinterpret_cast<uint32_t*>(emit_blk + 16);
         PinnedBuf* pb = nullptr;
         uint32_t nf = 0;
-        if (nrows)
+        // unsharded, one emit group: ordered on the device, the children deferred to emit().
+        // The ordering (k_rk_tables on k_freq_recs' row counts, k_rk_run on its runs) is
+        // launched behind k_freq_recs, before the host has the record count: its grids go by
+        // nrows and its buffers by cap.  The unordered records stay in HBM (Rd: k_rk_run reads
+        // them once more, not over the host link) and the ordered ones go to pinned memory;
+        // whatever drops the pass afterwards (overflow, the budget) finds every record of a
+        // pass that fitted there, in (row, slot) order, which the host ordering takes as well
+        uint32_t dmax = 0;
+        for (const ClassMeta& m : b.cls) dmax = std::max(dmax, m.D);
+        const size_t nko = size_t(b.cbase_total) + 1;
+        const bool ahead = !knobs.kids_host && order_device_applies(b, nrows, dmax, nko);
+        const RkRows rr{d_rows.as<DRow>(), b.gpu.d_cls.as<DClass>(), 0u};
+        DevBuf Rd, rowcnt, rowoff;
+        uint32_t cap_last = 0;
+        if (ahead) {
+            rowcnt.alloc(size_t(nrows) * 8);  // [count | kRkEven : nrows][run start : nrows]
+            rowoff.alloc((size_t(nrows) + 1) * 4);
+            b.gpu.ord_child_of.alloc(std::max<size_t>(nko - 1, 1) * 4);
+        }
+        if (nrows) {
+            uint64_t cap0 = std::min<uint64_t>(std::max<uint64_t>(uint64_t(nrows) * 4, 4096), b.n_cnt);
+            if (knobs.freq_cap) cap0 = std::min<uint64_t>(cap0, knobs.freq_cap);
             nf = extract_capped(
-                uint32_t(std::min<uint64_t>(std::max<uint64_t>(uint64_t(nrows) * 4, 4096), b.n_cnt)),
-                "SPADE: frequent candidate buffer overflow", [&](uint32_t cap, bool retry) {
-                    pb = ctx->pinned_big(size_t(std::max<uint32_t>(cap, 1)) * sizeof(FreqRec));
+                uint32_t(cap0), "SPADE: frequent candidate buffer overflow", [&](uint32_t cap, bool retry) {
+                    const size_t ncap = std::max<uint32_t>(cap, 1);
+                    pb = ctx->pinned_big(ncap * sizeof(FreqRec));
                     if (retry || dn == nullptr) {
                         if (d_n.p == nullptr) d_n.alloc(4);
                         dn = d_n.as<uint32_t>();
                         FSM_HIP(hipMemsetAsync(dn, 0, 4, s));
                     }
+                    FreqRec* out = static_cast<FreqRec*>(pb->dev);
+                    if (ahead) {
+                        Rd.alloc(ncap * sizeof(FreqRec));
+                        b.gpu.kid_tab.alloc((nko + 2 * ncap) * 4);
+                        out = Rd.as<FreqRec>();
+                    }
+                    cap_last = cap;
                     const size_t tk = clk->begin("k_freq_recs");
                     hipLaunchKernelGGL(k_freq_recs, dim3(grid), dim3(kBlock), 0, s, d_rows.as<DRow>(), nrows,
-                                       b.gpu.d_cls.as<DClass>(), cnt.as<uint32_t>(), minsup, rlo,
-                                       static_cast<FreqRec*>(pb->dev), cap, dn);
+                                       b.gpu.d_cls.as<DClass>(), cnt.as<uint32_t>(), minsup, rlo, out, cap, dn,
+                                       ahead ? rowcnt.as<uint32_t>() : (uint32_t*)nullptr);
                     FSM_LAUNCHED("k_freq_recs", s);
                     clk->end(tk, freq_bytes(b, nrows));
-                    if (ride && !retry) {
+                    const bool rode = ride && !retry;
+                    if (rode) {
                         FSM_HIP(hipMemcpyAsync(&pend[8], emit_blk, 24, hipMemcpyDeviceToHost, s));
                         emit_copied = true;
-                        sync();
-                        return uint32_t(pend[10] & 0xFFFFFFFFu);
+                    } else {
+                        FSM_HIP(hipMemcpyAsync(&pend[1], dn, 4, hipMemcpyDeviceToHost, s));
                     }
-                    FSM_HIP(hipMemcpyAsync(&pend[1], dn, 4, hipMemcpyDeviceToHost, s));
+                    if (ahead) {
+                        uint32_t* koff = b.gpu.kid_tab.as<uint32_t>();
+                        hipLaunchKernelGGL(k_rk_tables, dim3((nrows + kRkTile - 1) / kRkTile), dim3(kBlock), 0, s,
+                                           rowcnt.as<uint32_t>(), nrows, rr, uint32_t(nko), rowoff.as<uint32_t>(), koff,
+                                           b.gpu.ord_child_of.as<uint32_t>());
+                        FSM_LAUNCHED("k_rk_tables", s);
+                        hipLaunchKernelGGL(k_rk_run, dim3(grid), dim3(kBlock), 0, s, Rd.as<FreqRec>(),
+                                           rowcnt.as<uint32_t>(), rowoff.as<uint32_t>(), nrows, cap,
+                                           static_cast<FreqRec*>(pb->dev), koff + nko, koff + nko + ncap);
+                        FSM_LAUNCHED("k_rk_run", s);
+                        record_rec_ev(b);
+                    }
                     sync();
-                    return uint32_t(pend[1] & 0xFFFFFFFFu);
+                    return uint32_t((rode ? pend[10] : pend[1]) & 0xFFFFFFFFu);
                 });
-        // unsharded, one emit group: ordered on the device, the children deferred to emit()
-        if (nf && !comm && !knobs.kids_host) {
-            uint32_t dmax = 0;
-            for (const ClassMeta& m : b.cls) dmax = std::max(dmax, m.D);
-            if (order_device(b, pb, nf, nrows, RkRows{d_rows.as<DRow>(), b.gpu.d_cls.as<DClass>(), 0u}, dmax,
-                             size_t(b.cbase_total) + 1)) {
+        }
+        if (nf && ahead) {
+            const FreqRec* hr = static_cast<const FreqRec*>(pb->host);
+            uint64_t sumsup = 0;
+            if (order_device_fits(hr, nf, dmax, sumsup)) {
+                order_device_adopt(b, hr, nf, sumsup, nko, std::max<uint32_t>(cap_last, 1));
                 recs.clear();
                 return Records{nullptr, 0, false, false, true};
             }
@@ -4385,6 +4591,26 @@ struct Miner {
         }
         return db->pos_state > 0;
     }
+    // the DB's table for the bounded root F2 plan (k_f2_bound_tab), once per DB and row block
+    // geometry (rows per block; the blocks follow from it); false = over the size guard
+    static constexpr uint32_t kBoundGroups = 8192;  // rank groups whose u64 LDS sums k_f2_plan_bound holds (64 KiB)
+    bool ensure_f2_bound(const F2Geo& geo) {
+        const uint64_t U = uint64_t(db->U), bytes = uint64_t(geo.nblk) * U * 4;
+        if (U == 0 || U >= kNone || bytes > knobs.f2_tab_max || bytes > budget / 8) return false;
+        if (db->f2_bound_rpb == geo.rpb) return true;
+        db->f2_bound_rpb = 0;
+        db->f2_bound.alloc(bytes);
+        const int use_lds = U <= 16384;
+        if (!use_lds) FSM_HIP(hipMemsetAsync(db->f2_bound.p, 0, bytes, s));
+        const size_t tk = clk->begin("k_f2_bound_tab");
+        hipLaunchKernelGGL(k_f2_bound_tab, dim3(geo.nblk), dim3(kBlock), use_lds ? size_t(U) * 4 : 0, s,
+                           db->row_off.as<uint32_t>(), db->item.as<uint32_t>(), geo.R, geo.rpb, uint32_t(U),
+                           db->f2_bound.as<uint32_t>(), use_lds);
+        FSM_LAUNCHED("k_f2_bound_tab", s);
+        clk->end(tk, int64_t(db->R) * 4 + db->E * 4 + int64_t(bytes));
+        db->f2_bound_rpb = geo.rpb;
+        return true;
+    }
 
     // The DB-direct root: no root slab.  The F2 plan (key capacities per rank group and row
     // block, and the root entry count) is made from the DB rows; the F2 keys and the root
@@ -4416,11 +4642,18 @@ struct Miner {
         uint32_t G = geo.G;
         uint64_t nd = geo.nd;
         root.f2.tri = false;
+        size_t ig_off = 0;
         if (W == 1 && knobs.f2_tri) {
             std::vector<uint32_t> tab;
             const uint32_t rlo = geo.mlo / 2, rhi = geo.mhi == kNone ? F : std::min(geo.mhi / 2, F);
             const uint32_t TG = tri_tables(F, rlo, rhi, tab);
             if (TG) {
+                if (knobs.f2_bound && !comm && TG <= kBoundGroups) {
+                    // the bounded plan's item -> group table (kNone: infrequent), behind the group tables
+                    ig_off = tab.size();
+                    tab.resize(ig_off + size_t(db->U), kNone);
+                    for (uint32_t r = 0; r < F; ++r) tab[ig_off + freq_items[r]] = tab[r] >> kGroupShift;
+                }
                 upload_staged(1, root.f2.tri_tab, tab.data(), tab.size() * 4);
                 root.f2.tri = true;
                 root.f2.tri_G = TG;
@@ -4431,21 +4664,54 @@ struct Miner {
         root.f2.mem_db.alloc(std::max<int64_t>(db->E, 1) * 4);
         DevBuf cap(nd * 4);
         root.f2.base.alloc((nd + 1) * 8);
-        const size_t tk = clk->begin("k_f2_plan");
-        hipLaunchKernelGGL(k_f2_plan_db, dim3(geo.nblk), dim3(kF2Threads), size_t(G) * 4, s,
-                           db->row_off.as<uint32_t>(), db->item.as<uint32_t>(), root.f2.rk2.as<uint32_t>(), geo.R,
-                           geo.rpb, geo.pm, G, geo.nblk, geo.mlo, geo.mhi, cap.as<uint32_t>(), kF2Align - 1,
-                           root.f2.mem_db.as<uint32_t>(), root.f2.tri ? root.f2.tri_tab.as<uint32_t>() : nullptr);
-        FSM_LAUNCHED("k_f2_plan", s);
-        clk->end(tk, int64_t(db->R) * 4 + db->E * 8 + int64_t(nd) * 4);
-        scan_exclusive(cap.as<uint32_t>(), root.f2.base.as<uint64_t>(), nd, s);
-        pend[2] = 0;
-        FSM_HIP(hipMemcpyAsync(&pend[2], root.f2.base.as<uint64_t>() + nd, 8, hipMemcpyDeviceToHost, s));
+        // The plan.  Unsharded, unordered-pair layout: bounded from the DB's table S (a
+        // reduction of nblk x U values; the member ids then come from k_mem_db), else, or
+        // when the bound's slots pass the limits, exact from the rows
+        bool bound = ig_off != 0 && ensure_f2_bound(geo);
+        auto plan = [&](bool bnd) {
+            const size_t tk = clk->begin("k_f2_plan");
+            if (bnd) {
+                const uint32_t U = uint32_t(db->U);
+                hipLaunchKernelGGL(k_f2_plan_bound, dim3(geo.nblk), dim3(kF2Threads), size_t(G) * 8, s,
+                                   db->f2_bound.as<uint32_t>(), root.f2.tri_tab.as<uint32_t>() + ig_off, U, G, geo.nblk,
+                                   cap.as<uint32_t>(), kF2Align - 1);
+                FSM_LAUNCHED("k_f2_plan_bound", s);
+                // (two blocks of 1,024 threads per CU at most: each stages rk2 once)
+                const uint64_t E = uint64_t(db->E);
+                const int use_lds = U <= 16384;
+                const unsigned grid = unsigned(std::clamp<uint64_t>((E / 4 + kF2Threads - 1) / kF2Threads, 1, 512));
+                hipLaunchKernelGGL(k_mem_db, dim3(grid), dim3(kF2Threads), use_lds ? size_t(U) * 4 : 0, s,
+                                   db->item.as<uint32_t>(), root.f2.rk2.as<uint32_t>(), U, E,
+                                   root.f2.mem_db.as<uint32_t>(), use_lds);
+                FSM_LAUNCHED("k_mem_db", s);
+                clk->end(tk, int64_t(geo.nblk) * U * 4 + int64_t(nd) * 4 + db->E * 8);
+            } else {
+                hipLaunchKernelGGL(k_f2_plan_db, dim3(geo.nblk), dim3(kF2Threads), size_t(G) * 4, s,
+                                   db->row_off.as<uint32_t>(), db->item.as<uint32_t>(), root.f2.rk2.as<uint32_t>(), geo.R,
+                                   geo.rpb, geo.pm, G, geo.nblk, geo.mlo, geo.mhi, cap.as<uint32_t>(), kF2Align - 1,
+                                   root.f2.mem_db.as<uint32_t>(),
+                                   root.f2.tri ? root.f2.tri_tab.as<uint32_t>() : nullptr);
+                FSM_LAUNCHED("k_f2_plan", s);
+                clk->end(tk, int64_t(db->R) * 4 + db->E * 8 + int64_t(nd) * 4);
+            }
+            scan_exclusive(cap.as<uint32_t>(), root.f2.base.as<uint64_t>(), nd, s);
+            pend[2] = 0;
+            FSM_HIP(hipMemcpyAsync(&pend[2], root.f2.base.as<uint64_t>() + nd, 8, hipMemcpyDeviceToHost, s));
+        };
+        plan(bound);
         root_meta(root, freq_items, f1);
         // the root entries: one per (sequence, frequent item), so the frequent items' supports add up to them
         uint64_t E0 = 0;
         for (uint32_t it : freq_items) E0 += f1[it];
         sync();
+        if (bound && (pend[2] >= (uint64_t(1) << 32) - 4096 || pend[2] * 2 > budget)) {
+            bound = false;  // (the exact slots may still fit)
+            plan(false);
+            sync();
+        }
+        if (ctx->opts.verbose)
+            std::fprintf(stderr, "[fsm] root F2 plan: %s, %llu key slots\n", bound ? "bound" : "exact",
+                         (unsigned long long)pend[2]);
         if (E0 >= kNone) throw Error(FSM_ELIMIT, "SPADE: more than 2^32 root entries");
         if (pend[2] >= (uint64_t(1) << 32) - 4096) {  // region cursors are u32: the slab path counts it
             root.recycle();
