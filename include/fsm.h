@@ -365,6 +365,51 @@ void fsm_rules_free(fsm_rules* r);
 int fsm_rules_support(fsm_ctx* ctx, fsm_db* db, const fsm_rules* in, int32_t* support_out /* [in->n] */,
                       int32_t* ante_out /* [in->n], may be NULL */, double* confidence_out /* [in->n], may be NULL */);
 
+/* Per row of a resident TSR DB, the items that GIVEN rules say should come next, made on the
+ * GPU (an extension: the reference answers get:antecedent for one item list, on the host).
+ * By definition on the DB's rows (row = sequence = the caller's dense sid), for rule number r
+ * of `in`, r = X => Y, and a row s:
+ *   r fires in s      iff s holds every item of X; then fx = max over x in X of first_s(x)
+ *   y of Y is open    iff r fires in s and s does not hold y or last_s(y) <= fx (itemset
+ *                     indexes): y has not occurred strictly after X was complete.  An item
+ *                     the DB does not hold at all is open wherever r fires.  (r holds in s by
+ *                     fsm_rules_support's definition iff it fires and none of Y is open.)
+ *   rank              the rules in the order confidence descending, support descending, rule
+ *                     index ascending (in->support and in->confidence are read here; the
+ *                     doubles are compared on the host only)
+ *   best rule of (s, i)  the lowest-ranked rule under which i is open in s
+ * The list of s holds the items that have a best rule, ordered by the rank of their best rule,
+ * then by item value (two items share a best rule only through a multi-item Y), cut to its
+ * first topn entries.  Row s's entries are item[off[s] .. off[s+1]) (item VALUES) with
+ * rule[..] the index in `in` of the entry's best rule.  Equal rules are separate entries: the
+ * lower index wins, so the higher one is in no list on its own account.  A row in which
+ * nothing fires or nothing is open has an empty list.  The result does not depend on the
+ * order in which the DB's item -> sids lists were made.
+ * `in` is borrowed, never modified and may be caller-built; it is checked before any device
+ * work by the rules of fsm_rules_support (offsets monotone from 0, both sides non-empty,
+ * items strictly ascending inside a side, no item on both sides: FSM_EINVAL) and for non-NULL
+ * support and confidence when n > 0 and no NaN confidence (FSM_EINVAL).  topn < 1, a NULL
+ * argument, a db not of FSM_MODE_TSR or of another context: FSM_EINVAL.  n >= 2^31, or
+ * 2^32 - 2 or more items over all rules: FSM_ELIMIT; so is a single row with 2^31 or more
+ * (rule, open item) pairs.  A failed call leaves *out untouched.  n == 0 returns all-empty
+ * lists (off all 0); an unknown X item makes its rule dead.
+ * *out is a new library-owned result (fsm_predictions_free).  Nothing is built on the DB.
+ * Scratch grows with the (rule, open item) pairs of the rows, 32 bytes each, not with the
+ * output: a call whose pairs do not fit the context's budget (fsm_opts.mem_budget, else half
+ * of the free device memory) runs as several passes over row ranges, with the same result.
+ * A group context (ndevices > 1) answers from its rank 0's replica; with nranks > 1 each
+ * process answers from its own.  fsm_stats is left as it is; the kernel statistics become
+ * this call's (k_rp_*, k_scan). */
+typedef struct {
+    int64_t n;                  /* rows of the DB */
+    int64_t* off;               /* [n+1], off[0] = 0 */
+    int32_t* item;              /* [n_preds] item VALUES */
+    int32_t* rule;              /* [n_preds] index in `in` of the entry's best rule */
+    int64_t n_preds;            /* off[n] */
+} fsm_predictions;
+int fsm_rules_predict(fsm_ctx* ctx, fsm_db* db, const fsm_rules* in, int32_t topn, fsm_predictions** out);
+void fsm_predictions_free(fsm_predictions* p);   /* NULL is a no-op */
+
 /* Result persistence (SPADEActor.scala:47-68, TSRActor.scala:52-71): the
  * mined CSR rendered in bulk as the documents the actors hand to their sinks.
  *   fsm_patterns_serialize: one SPMF serialize() line per pattern,

@@ -1049,6 +1049,38 @@ int fsm_rules_support(fsm_ctx* ctx, fsm_db* db, const fsm_rules* in, int32_t* su
     return guarded(ctx, [&] { fsm::rules_support(ctx, db, in, support_out, ante_out, confidence_out); });
 }
 
+int fsm_rules_predict(fsm_ctx* ctx, fsm_db* db, const fsm_rules* in, int32_t topn, fsm_predictions** out) {
+    if (!ctx || !db || !in || !out) return fail(ctx, FSM_EINVAL, "fsm_rules_predict: null argument");
+    if (db->ctx != ctx) return fail(ctx, FSM_EINVAL, "fsm_rules_predict: db belongs to another context");
+    if (db->mode != FSM_MODE_TSR) return fail(ctx, FSM_EINVAL, "fsm_rules_predict: db was not flattened for TSR");
+    if (topn < 1) return fail(ctx, FSM_EINVAL, "fsm_rules_predict: topn must be >= 1 (got " + std::to_string(topn) + ")");
+    if (ctx->group) {
+        // rank 0's context and replica, on the calling thread, as fsm_rules_support runs
+        fsm::Group& g = *ctx->group;
+        if (!g.ready()) return group_finish(ctx, fsm::Group::kStalled);
+        if (db->parts.empty() || !db->parts[0]) return fail(ctx, FSM_EINVAL, "fsm_rules_predict: db has no replica on rank 0");
+        fsm_ctx* r0 = g.ranks[0];
+        const int rc = fsm_rules_predict(r0, db->parts[0], in, topn, out);
+        ctx->err = r0->err;
+        if (rc == FSM_OK) ctx->kstats = r0->kstats;
+        return rc;
+    }
+    // (nranks > 1: every process answers from its own replica; no collectives)
+    fsm_predictions* res = nullptr;  // (*out is written on success only)
+    const int rc = guarded(ctx, [&] { fsm::rules_predict(ctx, db, in, topn, &res); });
+    if (rc == FSM_OK) *out = res;
+    else fsm_predictions_free(res);
+    return rc;
+}
+
+void fsm_predictions_free(fsm_predictions* p) {
+    if (!p) return;
+    fsm::big_give(p->off);
+    fsm::big_give(p->item);
+    fsm::big_give(p->rule);
+    std::free(p);
+}
+
 // (result arrays may be big host blocks: fsm::big_give frees malloc'ed ones, caches the others)
 void fsm_patterns_free(fsm_patterns* p) {
     if (!p) return;

@@ -381,6 +381,12 @@ void sort_entry_keys(const uint64_t* keys, uint64_t* sorted, uint64_t n, unsigne
 // ante_out and confidence_out may be null
 void rules_support(fsm_ctx* ctx, fsm_db* db, const fsm_rules* in, int32_t* support_out, int32_t* ante_out,
                    double* confidence_out);
+// the CSR checks of fsm_rules_support (rule_support.hip): FSM_EINVAL / FSM_ELIMIT with `who` in
+// front of the message
+void rules_validate(const fsm_rules* in, const char* who);
+// per row of a resident TSR DB, the items given rules predict (rule_predict.hip); topn is
+// validated by the caller
+void rules_predict(fsm_ctx* ctx, fsm_db* db, const fsm_rules* in, int32_t topn, fsm_predictions** out);
 // FSM_HOST_PROF=<file>: SIGPROF sampling of the host side of a mine (host_prof.cpp)
 bool host_prof_start();
 void host_prof_stop();

@@ -195,6 +195,8 @@ void rs_validate(const fsm_rules* in, const char* who) {
 
 }  // namespace
 
+void rules_validate(const fsm_rules* in, const char* who) { rs_validate(in, who); }
+
 void rules_support(fsm_ctx* ctx, fsm_db* db, const fsm_rules* in, int32_t* support_out, int32_t* ante_out,
                    double* confidence_out) {
     const char* who = "fsm_rules_support";

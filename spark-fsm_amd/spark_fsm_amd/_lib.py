@@ -95,6 +95,16 @@ class SidLists(ctypes.Structure):
     ]
 
 
+class Predictions(ctypes.Structure):
+    _fields_ = [
+        ("n", ctypes.c_int64),
+        ("off", ctypes.POINTER(ctypes.c_int64)),
+        ("item", ctypes.POINTER(ctypes.c_int32)),
+        ("rule", ctypes.POINTER(ctypes.c_int32)),
+        ("n_preds", ctypes.c_int64),
+    ]
+
+
 class DbImage(ctypes.Structure):
     _fields_ = [
         ("mode", ctypes.c_int32),
@@ -154,6 +164,7 @@ EXPORTS = [
     "fsm_db_export", "fsm_db_image_free", "fsm_ingest", "fsm_token_db_free", "fsm_patterns_serialize",
     "fsm_patterns_json", "fsm_rules_json", "fsm_buffer_free", "fsm_rules_query", "fsm_patterns_filter",
     "fsm_patterns_support", "fsm_rules_support", "fsm_patterns_sids", "fsm_sidlists_free",
+    "fsm_rules_predict", "fsm_predictions_free",
 ]
 
 _lib = None
@@ -218,6 +229,10 @@ def load():
         L.fsm_sidlists_free.restype = None
     if hasattr(L, "fsm_rules_support"):
         L.fsm_rules_support.argtypes = [vp, vp, P(Rules), P(ctypes.c_int32), P(ctypes.c_int32), P(ctypes.c_double)]
+    if hasattr(L, "fsm_rules_predict"):
+        L.fsm_rules_predict.argtypes = [vp, vp, P(Rules), ctypes.c_int32, P(P(Predictions))]
+        L.fsm_predictions_free.argtypes = [P(Predictions)]
+        L.fsm_predictions_free.restype = None
     _lib = L
     return L
 

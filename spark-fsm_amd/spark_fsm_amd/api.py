@@ -128,6 +128,24 @@ def rule_supports(records_or_db, rules, engine=None):
         db.free()
 
 
+def rule_predictions(records_or_db, rules, topn, engine=None):
+    """What GIVEN scored rules (Engine.rule_predictions' forms) say should come next in every
+    sequence of a dataset of (sid, spmf_line) pairs (sids 0 .. n - 1), or of a TSR DB an engine
+    already holds (an extension) -> one list of (item, rule_index) pairs per row, best rule
+    first, topn entries at most."""
+    if hasattr(records_or_db, "handle"):
+        off, item, rule = records_or_db.engine.rule_predictions(records_or_db, rules, topn)
+    else:
+        eng = engine or default_engine()
+        db = eng.db_from_spmf(list(records_or_db), MODE_TSR)
+        try:
+            off, item, rule = eng.rule_predictions(db, rules, topn)
+        finally:
+            db.free()
+    off, pairs = off.tolist(), list(zip(item.tolist(), rule.tolist()))
+    return [pairs[off[s]:off[s + 1]] for s in range(len(off) - 1)]
+
+
 def spade_actor_patterns(patterns):
     """SPADEActor.train's mapping (SPADEActor.scala:47-58): serialize(), split on
     '|', support = trim.toInt, itemsets = split("-1") -> trim -> split(" ") -> toInt.

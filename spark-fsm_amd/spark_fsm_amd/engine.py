@@ -332,6 +332,41 @@ class Engine:
         del keep
         return sup[:n], ante[:n], conf[:n]
 
+    def rule_predictions(self, db, rules, topn, copy=False):
+        """fsm_rules_predict: per row of a resident TSR DB, the items GIVEN scored rules say
+        should come next -> (off int64[n + 1], item int32[n_preds], rule int32[n_preds]); row
+        s's entries are item[off[s]:off[s + 1]] (item values) with rule[...] the index of the
+        entry's best rule.
+
+        A rule X => Y fires in a row that holds all of X; an item of Y is open there if the
+        row does not hold it or holds it last no later than the itemset that completes X.  An
+        item's best rule is the first, by (confidence descending, support descending, index
+        ascending), under which it is open; a row lists its items by their best rule's rank,
+        then by value, topn at most.
+
+        rules is a MinedRules, a list of (X, Y, support, confidence) tuples as Engine.tsr
+        returns them, or a 6-tuple (ante_off, ante, cons_off, cons, support, confidence) of
+        arrays (see scored_rules_csr); a form without scores raises ValueError.  The arrays
+        are read-only views of the library's result with pattern_sids' ownership rules;
+        copy=True returns independent, writable copies."""
+        P = ctypes.POINTER
+        if isinstance(rules, MinedRules):
+            keep, ref = rules, rules._p  # the library's own struct, borrowed
+        else:
+            xo, xs, yo, ys, sup, conf = keep = scored_rules_csr(rules)
+            ref = ctypes.byref(_lib.Rules(len(xo) - 1, sup.ctypes.data_as(P(ctypes.c_int32)),
+                                          conf.ctypes.data_as(P(ctypes.c_double)), xo.ctypes.data_as(P(ctypes.c_int64)),
+                                          xs.ctypes.data_as(P(ctypes.c_int32)), yo.ctypes.data_as(P(ctypes.c_int64)),
+                                          ys.ctypes.data_as(P(ctypes.c_int32)), 0, 0))
+        out = P(_lib.Predictions)()
+        check(self._L.fsm_rules_predict(self._ctx, db.handle, ref, int(topn), ctypes.byref(out)), self._ctx)
+        del keep
+        owner = _ResultOwner(self._L.fsm_predictions_free, out)
+        r = out.contents
+        res = (owner.view(r.off, r.n + 1, np.int64), owner.view(r.item, r.n_preds, np.int32),
+               owner.view(r.rule, r.n_preds, np.int32))
+        return tuple(a.copy() for a in res) if copy else res
+
     def kernel_stats(self):
         """[{name, launches, alg_bytes, survey_bytes, ms}] of the last mine or filter call (device time, HIP
         events; alg_bytes: the kernel's own layout, survey_bytes: SURVEY §8(d) units)."""
@@ -413,6 +448,34 @@ def rules_csr(rules):
     if len(xo) < 1 or len(xo) != len(yo):
         raise ValueError("ante_off and cons_off must have the same n + 1 >= 1 entries")
     return xo, xs, yo, ys
+
+
+def scored_rules_csr(rules):
+    """The accepted forms of a SCORED rule set -> (ante_off int64[n+1], ante int32, cons_off
+    int64[n+1], cons int32, support int32[n], confidence float64[n]), the six arrays
+    fsm_rules_predict reads.  rules is a 6-tuple of such arrays (or lists), a MinedRules, or a
+    list of (X, Y, support, confidence) tuples.  A form without scores ((X, Y) pairs, the
+    4-tuple of rules_csr) raises ValueError."""
+    flat = (np.ndarray, list)
+    if isinstance(rules, MinedRules):
+        rules = rules.rules()
+    if (isinstance(rules, tuple) and len(rules) in (4, 6) and all(isinstance(a, flat) for a in rules)
+            and (len(rules[0]) == 0 or not hasattr(rules[0][0], "__len__"))):
+        if len(rules) == 4:
+            raise ValueError("rule predictions need scored rules: (ante_off, ante, cons_off, cons, support, confidence)")
+        xo, xs, yo, ys = rules_csr(tuple(rules[:4]))
+        sup, conf = rules[4], rules[5]
+    else:
+        rules = list(rules)
+        if any(len(r) < 4 for r in rules):
+            raise ValueError("rule predictions need scored rules: (X, Y, support, confidence) tuples")
+        xo, xs, yo, ys = rules_csr(rules)
+        sup, conf = [r[2] for r in rules], [r[3] for r in rules]
+    sup = np.ascontiguousarray(sup, np.int32)
+    conf = np.ascontiguousarray(conf, np.float64)
+    if len(sup) != len(xo) - 1 or len(conf) != len(xo) - 1:
+        raise ValueError("support and confidence must have one entry per rule")
+    return xo, xs, yo, ys, sup, conf
 
 
 class DB:
