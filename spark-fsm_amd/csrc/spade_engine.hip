@@ -1017,10 +1017,19 @@ __device__ __forceinline__ void tri_keys(uint64_t M0, uint64_t M1, uint64_t M2, 
 // d.y = (A + kTriA) | group << 16 with A = (first counter of its row) - 3 rank - 2, and the
 // mask: the key of (i -> j) is then A_i + 3 rank_j, that of the repeat A_i + 3 rank_i + 2 (the
 // row's first counter).
+//
+// One-kind step (the usual one: an item seldom sits in two itemsets of a sequence).  Two distinct
+// entries always have a key (their masks are non-empty, so with neither (i -> j) nor (j -> i)
+// lo_i >= hi_j >= lo_j >= hi_i >= lo_i: one common eid, the (i, j) key), so when no lane of the
+// step holds two kinds every ok lane but a run's first (the repeat) holds exactly one key.  The ok
+// lanes of a run are its first cnt lanes; the run's keys are then cnt - (first lane keyless),
+// lane st + q writes slot q - (first lane keyless), and one store writes them all: no prefix
+// counts and no totals to fetch.  Any other step takes tri_keys (wave-uniform choice).
 constexpr uint32_t kTriA = 32770u;
 __device__ __forceinline__ void tri_pair(uint64_t okm, uint32_t ie, uint32_t je, uint32_t st, uint32_t en,
-                                         const uint2* __restrict__ sd, const uint64_t* __restrict__ smk,
-                                         uint32_t* __restrict__ cur, uint16_t* __restrict__ keys) {
+                                         uint32_t cnt, const uint2* __restrict__ sd,
+                                         const uint64_t* __restrict__ smk, uint32_t* __restrict__ cur,
+                                         uint16_t* __restrict__ keys) {
     const bool ok = (okm >> lane_id()) & 1ull;
     const uint32_t qi = ok ? ie : 0u, qj = ok ? je : 0u;
     const uint2 Di = sd[qi], Dj = sd[qj];
@@ -1034,6 +1043,17 @@ __device__ __forceinline__ void tri_pair(uint64_t okm, uint32_t ie, uint32_t je,
     const uint64_t M2 = okm & ~sm & nz_mask(mm & mj);
     const bool t0 = ok && lo_i < hs, t1 = ok && !self && lo_j < hi_i, t2 = ok && !self && (mm & mj) != 0ull;
     const uint32_t key0 = (Di.y & 0xFFFFu) - kTriA + (Dj.x & 0xFFFFu) + (self ? 2u : 0u);
+    const uint64_t K = M0 | M1 | M2;
+    if (!((M0 & M1) | ((M0 | M1) & M2) | (okm & ~sm & ~K))) {  // (wave-uniform; the last term, a keyless partner, cannot be)
+        if (!K) return;
+        const bool has = t0 || t1 || t2;
+        const uint32_t sk = ok && !has;  // the run's first lane, keyless
+        uint32_t off = 0;
+        if (lane_id() == st && ok && cnt > sk) off = atomicAdd(&cur[Di.y >> 16], cnt - sk) - sk;
+        off = bperm(off, st);
+        if (has) keys[off + (lane_id() - st)] = uint16_t(key0 + (t0 ? 0u : t1 ? 1u : 2u));
+        return;
+    }
     tri_keys(M0, M1, M2, t0, t1, t2, key0, Di.y >> 16, st, en, cur, keys);
 }
 
@@ -1112,13 +1132,13 @@ __global__ __launch_bounds__(kF2Threads) void k_f2_tri(const uint32_t* __restric
                     const uint64_t okm = lt_mask(fp, npairs) & lt_mask(je, n) & (~sec | lt_mask(iA, iB));
                     // the run of lanes of ie: [s0, s0 + cA) for iA, [s0 + cA, s0 + S) for iB
                     const uint32_t st = second ? s0 + cA : s0, en = second ? s0 + S - 1u : s0 + cA - 1u;
-                    tri_pair(okm, ie, je, st, en, sd, smk, cur, keys);
+                    tri_pair(okm, ie, je, st, en, n - ie, sd, smk, cur, keys);
                 }
             } else {
                 for (uint32_t i = a0; i < a1; ++i)
                     for (uint32_t c0 = 0; i + c0 < n; c0 += 64) {
                         const uint32_t je = i + c0 + lane;
-                        tri_pair(lt_mask(je, n), i, je, 0u, 63u, sd, smk, cur, keys);
+                        tri_pair(lt_mask(je, n), i, je, 0u, 63u, min(n - i - c0, 64u), sd, smk, cur, keys);
                     }
             }
             __builtin_amdgcn_wave_barrier();
@@ -1147,7 +1167,18 @@ __global__ __launch_bounds__(kF2Threads) void k_f2_tri(const uint32_t* __restric
                     const bool t1 = ok && !self && lo_j < hi_i;
                     const bool t2 = ok && !self && (mki & mkj) != 0ull;
                     const uint32_t key0 = (gt & (kGroupCounters - 1u)) + (self ? 0u : 1u + 3u * ((mj >> 1) - ri - 1u));
-                    tri_keys(ballot(t0), ballot(t1), ballot(t2), t0, t1, t2, key0, gt >> kGroupShift, 0u, 63u, cur, keys);
+                    const uint64_t M0 = ballot(t0), M1 = ballot(t1), M2 = ballot(t2);
+                    if ((M0 & M1) | ((M0 | M1) & M2)) {
+                        tri_keys(M0, M1, M2, t0, t1, t2, key0, gt >> kGroupShift, 0u, 63u, cur, keys);
+                        continue;
+                    }
+                    // one kind per lane (infrequent partners leave gaps: one prefix count), one store
+                    const uint64_t K = M0 | M1 | M2;
+                    if (!K) continue;
+                    uint32_t off = 0;
+                    if (lane == 0) off = atomicAdd(&cur[gt >> kGroupShift], uint32_t(__popcll(K)));
+                    off = rfl(off);
+                    if (t0 || t1 || t2) keys[off + mbcnt64(K)] = uint16_t(key0 + (t0 ? 0u : t1 ? 1u : 2u));
                 }
             }
         }

@@ -103,5 +103,11 @@ def bible(D=36369, seed=1):
     return zipf(D, 13905, 1.05, 21.6, 0.7, 400, 0.25, False, seed, "bible-shaped-D%d" % D)
 
 
+def recur(D=100000, seed=1):
+    """Items that recur within a sequence, at most 64 itemsets (one mask word): nearly every
+    pair of a row's entries has more than one root F2 key (tools/f2_pair_stats.py)."""
+    return zipf(D, 1000, 1.0, 28.0, 0.4, 64, 0.3, False, seed, "recur-shaped-D%d" % D)
+
+
 def sign(D=730, seed=1):
     return zipf(D, 267, 0.8, 52.0, 0.35, 200, 0.3, False, seed, "sign-shaped-D%d" % D)

@@ -32,8 +32,8 @@ def kernel_name(demangled):
         return "k_emit"
     if base in ("k_count2", "k_sparse_keys"):  # the window / sparse counts: timed as "k_count"
         return "k_count"
-    if base == "k_f2_plan_db":  # the DB-direct root's F2 plan: timed as "k_f2_plan"
-        return "k_f2_plan"
+    if base in ("k_f2_plan_db", "k_f2_plan_bound", "k_mem_db"):  # the DB-direct root's F2 plan (exact, or bounded
+        return "k_f2_plan"                                      # with its member ids): timed as "k_f2_plan"
     if base == "k_f2_tri":  # the unordered-pair F2 key enumeration: timed as "k_f2_keys"
         return "k_f2_keys"
     return base

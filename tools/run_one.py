@@ -21,7 +21,7 @@ for p in (ROOT, os.path.join(ROOT, "spark-fsm_amd")):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("algo", choices=["spade", "tsr"])
-    ap.add_argument("shape", choices=["quest", "kosarak", "bible", "sign"])
+    ap.add_argument("shape", choices=["quest", "kosarak", "bible", "sign", "recur"])
     ap.add_argument("--D", type=int, default=0)
     ap.add_argument("--support", type=float, default=0.001)
     ap.add_argument("--k", type=int, default=1000)
