@@ -14,6 +14,11 @@ struct SpadeDevDB {
     fsm::DevBuf mask;     // u64 [E*W]
     int64_t R = 0, E = 0, U = 0;
     int W = 1;
+    // F1 (spade_engine.hip, k_f1): every item's distinct-sequence support, a property of the DB,
+    // kept by the handle's first unsharded mine; later unsharded mines filter it by their minsup
+    // without a pass over the items (sharded mines neither fill nor read it)
+    std::vector<uint32_t> f1_host;  // u32 [U]
+    bool f1_made = false;
     // the DB-direct root (spade_engine.hip): offset in row << 16 | row length of every
     // entry, made by the first mine that needs it; pos_state 0 = not made, 1 = made,
     // -1 = a row exceeds 65535 entries (that DB keeps the root slab)
@@ -22,9 +27,12 @@ struct SpadeDevDB {
     // the bounded root F2 plan's table (spade_engine.hip, k_f2_bound_tab): per row block b and
     // item u the sum of 1 + 3 (entries after it in its row) over u's entries in b, made by the
     // first mine that takes the bounded plan; f2_bound_rpb = the rows per block it was built
-    // for (0 = not made; rebuilt when a mine's row block geometry differs)
+    // for (0 = not made; rebuilt when a mine's row block geometry differs); f2_bound_sum = the
+    // sum of the whole table, read back once when it is built: with the regions' alignment it
+    // bounds the key slots of every mine of this DB, whatever its minsup
     fsm::DevBuf f2_bound;  // u32 [row blocks * U]
     uint32_t f2_bound_rpb = 0;
+    uint64_t f2_bound_sum = 0;
     // the vertical index (pattern_support.hip): item i's entries are vert[vert_off[i] ..
     // vert_off[i+1]), each (row, entry index); made by the first fsm_patterns_support on this
     // DB (vert_state 0 = not made, 1 = made, in no particular order inside a list, 2 = made

@@ -13,7 +13,8 @@
 // Runs are laid out in parent-entry order (see k_emit).
 //
 // Kernels, in the order a mine launches them:
-//   k_f1           F1: distinct-sequence support of every item.
+//   k_f1           F1: distinct-sequence support of every item (unsharded: a handle's first
+//                  mine only, the histogram stays with the DB).
 //   root           the root class is the flattened DB restricted to the frequent items.
 //                  DB-direct (default): no root slab, k_db_pos (row positions, once per
 //                  DB) and k_f2_plan_db (key capacities per rank group and row block)
@@ -706,10 +707,13 @@ __global__ __launch_bounds__(kF2Threads) void k_f2_plan_db(const uint32_t* __res
 // partners after it are at most the entries after it: S bounds the exact capacity item by
 // item.  (An item occurs once per row and rows hold at most 65535 entries: a sum over the at
 // most kF2MaxRows rows of a block stays below 2^32.)  LDS counters when the items fit (k_f1's
-// bound), else global atomics on the zeroed table.
+// bound), else global atomics on the zeroed table.  *total (zeroed) takes the sum of the whole
+// table (a row of n entries adds n + 3 n (n - 1) / 2), one atomic per wave: the host adds the
+// regions' alignment to it and has a bound of every mine's key slots (run_root_db).
 __global__ __launch_bounds__(kBlock) void k_f2_bound_tab(const uint32_t* __restrict__ row_off,
                                                          const uint32_t* __restrict__ item, uint32_t R, uint32_t rpb,
-                                                         uint32_t U, uint32_t* __restrict__ S, int use_lds) {
+                                                         uint32_t U, uint32_t* __restrict__ S, int use_lds,
+                                                         unsigned long long* __restrict__ total) {
     extern __shared__ __attribute__((aligned(16))) uint32_t h[];
     uint32_t* out = S + size_t(blockIdx.x) * U;
     if (use_lds) {
@@ -717,14 +721,18 @@ __global__ __launch_bounds__(kBlock) void k_f2_bound_tab(const uint32_t* __restr
         __syncthreads();
     }
     const uint32_t r0 = blockIdx.x * rpb, r1 = min(R, r0 + rpb);
+    unsigned long long acc = 0;
     for (uint32_t r = r0 + (threadIdx.x >> 6); r < r1; r += kBlock / 64) {
         const uint32_t rb = row_off[r], e1 = row_off[r + 1];
         for (uint32_t e = rb + lane_id(); e < e1; e += 64) {
             const uint32_t w = 1u + 3u * (e1 - 1u - e);
+            acc += w;
             if (use_lds) atomicAdd(&h[item[e]], w);
             else atomicAdd(&out[item[e]], w);
         }
     }
+    acc = wave_incl_scan(acc);  // (every lane of a wave leaves the row loop together: r is wave-uniform)
+    if (lane_id() == 63 && acc) atomicAdd(total, acc);
     if (use_lds) {
         __syncthreads();
         for (uint32_t u = threadIdx.x; u < U; u += blockDim.x) out[u] = h[u];
@@ -2499,6 +2507,9 @@ template <class F> void with_window_width(int W, F&& f) {
 //   FSM_F2_TRI        0: the ordered-pair root F2 (k_f2_keys) instead of k_f2_tri
 //   FSM_F2_PLAN       exact: the root F2 plan walked from the DB rows every mine (k_f2_plan_db);
 //                     bound (default): summed from the DB's table (unsharded W = 1 unordered-pair roots)
+//   FSM_F1_CACHE      0: k_f1 runs every mine (default: an unsharded handle keeps its F1 supports)
+//   FSM_F2_AHEAD      0: k_f2_tri waits for the plan's slot total (default: launched behind the scan
+//                     where the DB's key bound passes the limits; bounded plan only)
 //   FSM_F2_TAB_MAX    size guard of that table in bytes (256 MiB; a test hook: 0 forces the exact plan)
 //   FSM_F2_BLOCKS     target row blocks of the root F2, [1, kF2MaxBlocks] (1024)
 //   FSM_COUNT_KERNEL  thread: k_count for every batch (default: k_count2 where W has it)
@@ -2525,6 +2536,7 @@ struct SpadeKnobs {
     uint64_t keyed_min;
     bool root_atomic, root_db, f2_tri;
     bool f2_bound;
+    bool f1_cache, f2_ahead;
     uint64_t f2_tab_max;
     uint32_t f2_blocks;
     bool count_window;  // k_count2 where the width has it
@@ -2563,6 +2575,8 @@ struct SpadeKnobs {
         k.root_db = !lead("FSM_ROOT_DB", '0');
         k.f2_tri = !lead("FSM_F2_TRI", '0');
         k.f2_bound = !is("FSM_F2_PLAN", "exact");
+        k.f1_cache = !lead("FSM_F1_CACHE", '0');
+        k.f2_ahead = !lead("FSM_F2_AHEAD", '0');
         k.f2_tab_max = num("FSM_F2_TAB_MAX", uint64_t(256) << 20);
         k.f2_blocks = uint32_t(clamped("FSM_F2_BLOCKS", 1, kF2MaxBlocks, 1024));
         k.count_window = !is("FSM_COUNT_KERNEL", "thread");
@@ -2762,6 +2776,9 @@ struct BatchRootF2 {
     bool planned = false;
     DevBuf base;
     uint64_t nslots = 0;
+    // k_f2_tri launched ahead of the slot total's read-back: nslots holds the DB's bound (the key
+    // buffer's size) until root_f2_tri has the scanned total, at the sync behind k_f2_count
+    bool ahead = false;
     // the unordered-pair layout (k_f2_tri): [gtab: F | group start ranks: G + 1]
     bool tri = false;
     DevBuf tri_tab;
@@ -2954,6 +2971,9 @@ struct Miner {
         check_emit();
     }
     uint64_t* pend = nullptr;  // pinned slots (ctx->pinned_u64()): [8..10] the last emit's cursor block
+    // [7] the bounded plan table's sum (ensure_f2_bound); [11] the root F2 plan's slot total when
+    // k_f2_tri was launched ahead of it (read at the sync behind k_f2_count, which rewrites [2])
+    static constexpr int kPendSum = 7, kPendSlots = 11;
     char* emit_blk = nullptr;  // the last emit's 32-byte device block (cursor, long runs, flag, next count)
     bool emit_copied = false;  // its read-back is enqueued
     DevBuf emit_own;           // (the block when the zeroed slots are used up)
@@ -3444,7 +3464,7 @@ struct Miner {
                            b.f2.base.as<uint64_t>(), b.f2.fill.as<uint32_t>(), b.f2.keys.as<uint16_t>(),
                            reinterpret_cast<unsigned long long*>(b.f2.ctr));
         FSM_LAUNCHED("k_f2_tri", s);
-        clk->end(b.f2.tk, db->E * 12 + int64_t(nd) * 12, int64_t(b.cls[0].cap) * 8);
+        clk->end(b.f2.tk, db->E * 12 + int64_t(nd) * 12, int64_t(b.E) * 8);  // (b.E: the root class's entries)
         b.f2.launched = true;
         return true;
     }
@@ -3480,6 +3500,18 @@ struct Miner {
                 clk->end(tk_cnt, int64_t(G) * nblk * 12);
                 return read_f2_counts(ctr);
             });
+        if (b.f2.ahead) {
+            // the plan's scanned total came back with the counts (run_root_db enqueued its copy
+            // behind k_f2_tri, which ran in a buffer of the DB's bound)
+            const uint64_t bnd = b.f2.nslots;
+            b.f2.nslots = pend[kPendSlots];
+            b.f2.ahead = false;
+            if (ctx->opts.verbose)
+                std::fprintf(stderr, "[fsm] root F2 plan: bound, %llu key slots\n", (unsigned long long)b.f2.nslots);
+            if (b.f2.nslots > bnd)
+                throw Error(FSM_EDEVICE, "SPADE internal error: root F2 plan of " + std::to_string(b.f2.nslots) +
+                                             " key slots exceeds the DB's bound " + std::to_string(bnd));
+        }
         root_f2_account(tk_keys, tk_cnt, nrec);
         double tr = now_ms();
         const bool on_device =
@@ -4630,15 +4662,23 @@ struct Miner {
         if (U == 0 || U >= kNone || bytes > knobs.f2_tab_max || bytes > budget / 8) return false;
         if (db->f2_bound_rpb == geo.rpb) return true;
         db->f2_bound_rpb = 0;
+        db->f2_bound_sum = 0;
         db->f2_bound.alloc(bytes);
         const int use_lds = U <= 16384;
         if (!use_lds) FSM_HIP(hipMemsetAsync(db->f2_bound.p, 0, bytes, s));
+        DevBuf tot_own;
+        char* tot = zeroed_slot(8, tot_own);
         const size_t tk = clk->begin("k_f2_bound_tab");
         hipLaunchKernelGGL(k_f2_bound_tab, dim3(geo.nblk), dim3(kBlock), use_lds ? size_t(U) * 4 : 0, s,
                            db->row_off.as<uint32_t>(), db->item.as<uint32_t>(), geo.R, geo.rpb, uint32_t(U),
-                           db->f2_bound.as<uint32_t>(), use_lds);
+                           db->f2_bound.as<uint32_t>(), use_lds, reinterpret_cast<unsigned long long*>(tot));
         FSM_LAUNCHED("k_f2_bound_tab", s);
         clk->end(tk, int64_t(db->R) * 4 + db->E * 4 + int64_t(bytes));
+        // the table's sum, once per table: the only read-back the key bound of later mines needs
+        pend[kPendSum] = 0;
+        FSM_HIP(hipMemcpyAsync(&pend[kPendSum], tot, 8, hipMemcpyDeviceToHost, s));
+        sync();
+        db->f2_bound_sum = pend[kPendSum];
         db->f2_bound_rpb = geo.rpb;
         return true;
     }
@@ -4699,6 +4739,15 @@ struct Miner {
         // reduction of nblk x U values; the member ids then come from k_mem_db), else, or
         // when the bound's slots pass the limits, exact from the rows
         bool bound = ig_off != 0 && ensure_f2_bound(geo);
+        // The key bound of this DB and geometry: the table's sum with every region rounded up
+        // to the alignment bounds the scanned slot total at any minsup.  Where it passes the
+        // u32 cursor limit and the budget, nothing the read-back says changes what is launched:
+        // k_f2_tri goes right behind the scan, into a key buffer of the bound's size, and the
+        // total is read at the sync behind k_f2_count (root_f2_tri).  On no weaker condition:
+        // a total over the cursor limit would wrap the cursors and write outside the buffer.
+        const uint64_t kbound = db->f2_bound_sum + uint64_t(kF2Align - 1) * nd;
+        const bool ahead =
+            bound && knobs.f2_ahead && kbound < (uint64_t(1) << 32) - 4096 && kbound * 2 <= budget;
         auto plan = [&](bool bnd) {
             const size_t tk = clk->begin("k_f2_plan");
             if (bnd) {
@@ -4726,18 +4775,41 @@ struct Miner {
                 clk->end(tk, int64_t(db->R) * 4 + db->E * 8 + int64_t(nd) * 4);
             }
             scan_exclusive(cap.as<uint32_t>(), root.f2.base.as<uint64_t>(), nd, s);
-            pend[2] = 0;
-            FSM_HIP(hipMemcpyAsync(&pend[2], root.f2.base.as<uint64_t>() + nd, 8, hipMemcpyDeviceToHost, s));
+        };
+        // the slot total's read-back: ahead of the sync that checks it, or behind k_f2_tri's launch
+        auto read_total = [&](int slot) {
+            pend[slot] = 0;
+            FSM_HIP(hipMemcpyAsync(&pend[slot], root.f2.base.as<uint64_t>() + nd, 8, hipMemcpyDeviceToHost, s));
         };
         plan(bound);
-        root_meta(root, freq_items, f1);
         // the root entries: one per (sequence, frequent item), so the frequent items' supports add up to them
         uint64_t E0 = 0;
         for (uint32_t it : freq_items) E0 += f1[it];
+        if (ahead) {
+            if (E0 >= kNone) throw Error(FSM_ELIMIT, "SPADE: more than 2^32 root entries");
+            if (ctx->opts.verbose)
+                std::fprintf(stderr, "[fsm] root F2 keys ahead: bound %llu\n", (unsigned long long)kbound);
+            root.E = E0;
+            root.R = uint64_t(db->R);
+            root.f2.planned = true;
+            root.f2.nslots = kbound;
+            root.f2.ahead = true;
+            root.db_direct = true;
+            // (the class record comes after the launch: the host builds it while the keys are written)
+            (void)launch_f2_tri(root, f2_geometry(root, 2 * F, E0, uint64_t(db->R)));
+            read_total(kPendSlots);
+            root_meta(root, freq_items, f1);
+            root.cls[0].cap = E0;
+            ctx->stats.root_entries = int64_t(E0);
+            return true;
+        }
+        read_total(2);
+        root_meta(root, freq_items, f1);
         sync();
         if (bound && (pend[2] >= (uint64_t(1) << 32) - 4096 || pend[2] * 2 > budget)) {
             bound = false;  // (the exact slots may still fit)
             plan(false);
+            read_total(2);
             sync();
         }
         if (ctx->opts.verbose)
@@ -4991,9 +5063,13 @@ void spade_mine(fsm_ctx* ctx, fsm_db* db, double support, fsm_patterns** out) {
     FSM_HIP(hipMemsetAsync(mn.zblk.p, 0, Miner::kZBytes, ctx->stream));
     mn.d_tests = static_cast<unsigned long long*>(mn.zslot(8));
 
-    // ---- F1 (K1)
-    std::vector<uint32_t> f1(size_t(d->U), 0);
-    {
+    // ---- F1 (K1): an item's distinct-sequence support is the DB's, whatever the minsup: an
+    // unsharded handle keeps the histogram of its first mine (FSM_F1_CACHE=0: every mine counts)
+    const bool f1_keep = !comm && mn.knobs.f1_cache;
+    std::vector<uint32_t> f1_own;
+    if (!(f1_keep && d->f1_made)) {
+        f1_own.assign(size_t(d->U), 0);
+        std::vector<uint32_t>& f1 = f1_own;
         DevBuf d_f1(std::max<int64_t>(d->U, 1) * 4);
         FSM_HIP(hipMemsetAsync(d_f1.p, 0, size_t(d->U) * 4, ctx->stream));
         // sharded: each rank histograms its slice of the entries, then one all-reduce
@@ -5014,7 +5090,12 @@ void spade_mine(fsm_ctx* ctx, fsm_db* db, double support, fsm_patterns** out) {
         if (d->U) FSM_HIP(hipMemcpyAsync(pb->host, d_f1.p, size_t(d->U) * 4, hipMemcpyDeviceToHost, ctx->stream));
         FSM_HIP(hipStreamSynchronize(ctx->stream));
         if (d->U) std::memcpy(f1.data(), pb->host, size_t(d->U) * 4);
+        if (f1_keep) {
+            d->f1_host = std::move(f1_own);
+            d->f1_made = true;
+        }
     }
+    const std::vector<uint32_t>& f1 = f1_keep ? d->f1_host : f1_own;
     std::vector<uint32_t> freq;
     if (!none)
         for (int64_t i = 0; i < d->U; ++i)

@@ -2,13 +2,19 @@
 
     python tools/ktrace_gaps.py gpurun_out/ktrace/d1m/run_kernel_trace.csv [--mine N]
 
-Splits the trace into mines at each launch of the kernel named by --start (default
-k_f1, the first kernel of a SPADE mine), takes mine N (default: the last one), and prints every kernel in order with the
-idle time before it, then the busy / idle totals: the host's share of a mine.
+Splits the trace into mines (tools/mine_split.py: at k_f1 where a mine has one, a DB handle's
+first, else at its first root plan kernel with the small launches before it; --start NAME
+splits at that kernel only), takes mine N (from 0; default: the last one; what precedes the
+first mine is not counted), and prints every kernel in order with the idle time before it,
+then the busy / idle totals: the host's share of a mine.
 """
 import csv
+import os
 import re
 import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import mine_split  # noqa: E402
 
 
 def short(name):
@@ -27,14 +33,7 @@ def main():
         for r in csv.DictReader(f):
             rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), short(r["Kernel_Name"])))
     rows.sort()
-    mines, cur = [], []
-    for r in rows:
-        if cur and r[2] == start:
-            mines.append(cur)
-            cur = []
-        cur.append(r)
-    if cur:
-        mines.append(cur)
+    mines = mine_split.split(rows, lambda r: r[2], start)
     m = mines[pick]
     t0, busy, idle, prev = m[0][0], 0, 0, m[0][0]
     for s, e, n in m:

@@ -3,9 +3,10 @@
 Usage (each pass is its own rocprofv3 run of a bench command, see tools/round_evidence.sh):
     python tools/pmc_summary.py [--last-mine] OUT.json DIR_FETCH DIR_WRITE [more dirs...]
 
---last-mine keeps only the dispatches from the last k_f1 on (the last SPADE mine of
-the run: a bench run of a warmup step and one step then reports the steady state,
-without the DB build's one-time kernels and fills).
+--last-mine keeps only the dispatches of the last SPADE mine of the run (tools/mine_split.py:
+from its k_f1 on, or, for a handle's later mines, which have none, from its root plan and the
+small launches before it): a bench run of a warmup step and one step then reports the steady
+state, without the DB build's one-time kernels and fills.
 
 For every kernel (named as libfsm's fsm_get_kernel_stats names it) the JSON has
 the counter totals over the step's dispatches, in bytes (rocprofv3 reports
@@ -19,6 +20,9 @@ import json
 import os
 import re
 import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import mine_split  # noqa: E402
 
 
 def kernel_name(demangled):
@@ -48,12 +52,22 @@ def read_dir(d):
 
 
 def last_mine(rows):
-    """the rows of the dispatches from the last k_f1 on (Dispatch_Id order)"""
-    ids = [int(r.get("Dispatch_Id", 0) or 0) for r in rows if kernel_name(r.get("Kernel_Name", "")) == "k_f1"]
-    if not ids:
+    """the rows of the last mine's dispatches (Dispatch_Id order; a pass has a row per counter and dispatch)"""
+    return nth_mine(rows, -1)
+
+
+def nth_mine(rows, n):
+    did = lambda r: int(r.get("Dispatch_Id", 0) or 0)
+    names = {}
+    for r in rows:
+        names.setdefault(did(r), r.get("Kernel_Name", ""))
+    ids = sorted(names)
+    s = mine_split.starts([names[i] for i in ids])
+    if not s:
         return rows
-    first = max(ids)
-    return [r for r in rows if int(r.get("Dispatch_Id", 0) or 0) >= first]
+    s.append(len(ids))
+    keep = set(ids[s[n]:s[n + 1]] if n >= 0 else ids[s[n - 1]:s[n]])
+    return [r for r in rows if did(r) in keep]
 
 
 def main():
